@@ -15,7 +15,11 @@ synchronize + barrier; value = all ranks' chunk bytes * K / max-over-ranks
 wall time, in GiB/s.  The hot kernel's own duration is also taken live with
 HIP events on the stream it is launched on, for the roofline.
 
-After the timed region:
+A plain run stops there: set up, warm up, time the K steps, write the timed
+path's digests if --dump-outputs is given, print the line (the legs below
+null).  Everything else is measured only with --full.
+
+After the timed region, with --full:
   * every rank: the in-kernel shader clock of the hot kernel (stamped
     diagnostic build, bt_sha1_clock_probe), so the VALU roofline is priced
     at the clock the chip actually held as well as at the nominal 2.4 GHz;
@@ -752,6 +756,30 @@ def host_paths(bt, torch, dev_buf, host, want, verify_gib=1):  # noqa: C901
     return out
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirpath, digests, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what the timed path's last step returned -- every
+    rank's 20-byte digests in global chunk order -- as DIR/digests.npy,
+    float32 [chunks, 20] (one byte value per element).  A batch whose dump
+    would pass max_bytes is sampled: a fixed, seeded choice of rows (sorted),
+    their global chunk indices beside them in DIR/digest_rows.npy (float64).
+    Returns the names written."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    d = np.frombuffer(digests, dtype=np.uint8).reshape(-1, 20)
+    names = ["digests"]
+    cap = max_bytes // (20 * 4 + 8) - 4  # a float32 row and its float64 index; the .npy headers
+    if d.shape[0] > cap:
+        rows = np.sort(np.random.default_rng(SEED).choice(d.shape[0], cap, replace=False))
+        d = d[rows]
+        np.save(os.path.join(dirpath, "digest_rows.npy"), rows.astype(np.float64))
+        names.append("digest_rows")
+    np.save(os.path.join(dirpath, "digests.npy"), d.astype(np.float32))
+    return names
+
+
 def find_traffic(want, path=None):
     """(HBM bytes per launch, note) from the PMC traffic file measured on this
     very build -- source id, kernel, variant and layout all equal to `want` --
@@ -800,6 +828,13 @@ def main():
     ap.add_argument("--digest-sample", type=int, default=3,
                     help="digests of this many chunks of EVERY rank (first, last, evenly between) in the line, "
                          "for parity checks beyond the golden range (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other leg: in-kernel clock, board power, parity "
+                         "against the golden digests, CPU baseline, verify_dev and the host paths (each still "
+                         "switched off by its own option); without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the digests of the last timed step (all ranks, global chunk order) to "
+                         "DIR/digests.npy as float32 [chunks, 20]; above 64 MB a fixed seeded sample of rows")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="allow N > 1 ranks on fewer than N distinct GPUs (a rehearsal of the rank path on one "
                          "GPU, recorded in the line); without it such a launch exits before the timed region")
@@ -876,7 +911,7 @@ def main():
     # after the timed region), so a slow rank of an N-GPU line is attributable
     # to its clock or to its kernel without a second run.
     clock, rank_mhz = None, None
-    if not args.no_clock and kernel == "k_sha1_fixed":
+    if args.full and not args.no_clock and kernel == "k_sha1_fixed":
         mine, err = [-1.0, 0.0], None
         try:
             mhz, same = hasher.clock_mhz()
@@ -902,7 +937,7 @@ def main():
 
     # Every rank measures its own GPU's power (all ranks run the window together).
     power = None
-    if args.power_s > 0:
+    if args.full and args.power_s > 0:
         try:
             power = power_window(hasher, torch, dev, args.power_s)
         except Exception as e:  # noqa: BLE001 -- the power evidence must never cost the bench line
@@ -930,7 +965,7 @@ def main():
         # committed golden vectors (tests/golden/synth4096.txt, from sha.c).
         parity = None
         golden = os.path.join(HERE, "tests", "golden", "synth4096.txt")
-        if os.path.exists(golden) and world * C >= 4096:
+        if args.full and os.path.exists(golden) and world * C >= 4096:
             rows = [l.split() for l in open(golden) if not l.startswith("#")]
             parity = all(all_dig[20 * int(i):20 * int(i) + 20].hex() == h for i, h in rows)
 
@@ -938,7 +973,7 @@ def main():
         # GLOBAL chunk index: the tests recompute them with the oracle on
         # regenerated chunks, covering ranks >= 1 beyond the golden range.
         sample = None
-        if args.digest_sample > 0:
+        if args.full and args.digest_sample > 0:
             sample = [{"rank": r, "chunk": g, "sha1": all_dig[20 * g:20 * g + 20].hex()}
                       for r, g in shard.sample_chunks(world, C, args.digest_sample)]
 
@@ -946,7 +981,7 @@ def main():
         # concatenated 20-byte digests, hashlib): the tests compare it with the
         # oracle's digests of every regenerated chunk of every rank.
         import hashlib
-        digests_sha1 = hashlib.sha1(all_dig).hexdigest() if all_dig else None
+        digests_sha1 = hashlib.sha1(all_dig).hexdigest() if args.full and all_dig else None
         # ... and against the REFERENCE's checksum for this many global chunks
         # (tests/golden/synth_checksums.txt, sha.c's digests of the same
         # chunks): every digest of the run, every rank, in one comparison.
@@ -963,15 +998,21 @@ def main():
         traffic, traffic_note = find_traffic(want, args.traffic_json)
         phase("gather_and_parity_s")
 
+        dumped = None
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, all_dig)
+            phase("dump_outputs_s")
+
         # Rank 0 runs the CPU baseline at every N (the other ranks wait at the
         # final barrier, their GPUs idle): each line carries the reference
         # sha.c on this node's host cores from the same run (north_star).
         # The host paths (config 5) are a one-GPU measurement (N = 1 only).
-        want_host = world == 1 and not args.no_host_path
+        want_cpu = args.full and not args.no_cpu_baseline
+        want_host = args.full and world == 1 and not args.no_host_path
         extras_host = None
-        if not args.no_cpu_baseline or want_host:
+        if want_cpu or want_host:
             import numpy as np
-            n_host = min(C, max(args.cpu_chunks if not args.no_cpu_baseline else 0,
+            n_host = min(C, max(args.cpu_chunks if want_cpu else 0,
                                 int(args.host_gib * 2**30) // CHUNK if want_host else 0))
             extras_host = np.empty(n_host * CHUNK, dtype=np.uint8)
             view = torch.from_numpy(extras_host)
@@ -984,7 +1025,7 @@ def main():
                         view[j * CHUNK:(j + 1) * CHUNK].copy_(hasher.buf[j * pitch:j * pitch + CHUNK])
 
         cpu = None
-        if not args.no_cpu_baseline:
+        if want_cpu:
             try:
                 cpu = cpu_baseline(extras_host.ctypes.data, min(args.cpu_chunks, C), all_dig)
             except Exception as e:  # the checker must never cost the bench line
@@ -992,7 +1033,7 @@ def main():
             phase("cpu_baseline_s")
 
         verify = None
-        if world == 1:
+        if args.full and world == 1:
             try:
                 verify = hasher.verify_rate()
             except Exception as e:  # noqa: BLE001 -- never costs the bench line
@@ -1059,6 +1100,9 @@ def main():
             "aggregate_kernel_GiB_per_s": round(world * C * CHUNK / (kern_max * 1e-3) / 2**30, 3),
             "distinct_gpus": shard.distinct_devices(idents),
             "rehearse_shared_gpu": bool(args.rehearse_shared_gpu),
+            # False: a plain run -- the legs measured after the timed region are null
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
             "parity_first_4096_vs_golden": parity,
             "digest_sample": sample,
             "digests_sha1": digests_sha1,

@@ -167,6 +167,30 @@ def test_ensure_built_adds_the_experiments_library_only_for_variants(monkeypatch
     assert len(calls) == 1 and calls[0][-1] == "experiments" and "lib" in calls[0]
 
 
+def test_dump_outputs_writes_the_digests_as_float32(tmp_path):
+    """--dump-outputs: DIR/digests.npy holds every digest, one float32 per
+    byte, [chunks, 20] in the order given; a dump that would pass the size
+    limit keeps a seeded sample of rows -- the same rows on every call -- with
+    their chunk indices beside it, and stays under the limit."""
+    import numpy as np
+    b = _bench()
+    raw = bytes((7 * i + i // 20) % 256 for i in range(20 * 1000))
+    assert b.dump_outputs(str(tmp_path / "all"), raw) == ["digests"]
+    d = np.load(tmp_path / "all" / "digests.npy")
+    assert d.dtype == np.float32 and d.shape == (1000, 20) and d.astype(np.uint8).tobytes() == raw
+    assert os.listdir(tmp_path / "all") == ["digests.npy"]
+    limit = 88 * 300
+    for name in ("s1", "s2"):
+        assert b.dump_outputs(str(tmp_path / name), raw, max_bytes=limit) == ["digests", "digest_rows"]
+    d, rows = np.load(tmp_path / "s1" / "digests.npy"), np.load(tmp_path / "s1" / "digest_rows.npy")
+    assert d.dtype == np.float32 and rows.dtype == np.float64 and len(d) == len(rows) > 250
+    assert list(rows) == sorted(set(rows)) and 0 <= rows[0] and rows[-1] < 1000
+    assert all(d[k].astype(np.uint8).tobytes() == raw[20 * int(g):20 * int(g) + 20] for k, g in enumerate(rows))
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "digest_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= limit
+    assert b.DUMP_MAX_BYTES <= 64 * 2**20
+
+
 @pytest.mark.parametrize("bad", [["--steps", "0"], ["--warmup", "-1"], ["--chunks", "0"], ["--gpus", "0"]])
 def test_degenerate_arguments_exit_before_torch(bad):
     """A line needs at least one timed step over at least one chunk on at

@@ -49,7 +49,8 @@ def _run_bench(world, chunks, *extra, timeout=240, launcher=True, shared=True):
     N > 1 way (torch.distributed.run) or, launcher=False, as the plain
     `python bench.py --gpus N` the driver may also run (bench.py starts the
     ranks itself).  All ranks share the one GPU, so the run needs
-    --rehearse-shared-gpu (shared=True); without it bench.py must refuse."""
+    --rehearse-shared-gpu (shared=True); without it bench.py must refuse.
+    Always --full: the tests read the legs measured after the timed region."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     if not shared:
@@ -57,7 +58,7 @@ def _run_bench(world, chunks, *extra, timeout=240, launcher=True, shared=True):
         # of the devices this process may use
         vis = env.get("HIP_VISIBLE_DEVICES") or env.get("CUDA_VISIBLE_DEVICES")
         env["HIP_VISIBLE_DEVICES"] = vis.split(",")[0] if vis else "0"
-    args = [os.path.join(REPO, "bench.py"), "--gpus", str(world), "--chunks", str(chunks),
+    args = [os.path.join(REPO, "bench.py"), "--full", "--gpus", str(world), "--chunks", str(chunks),
             "--steps", "3", "--warmup", "1", *extra] + (["--rehearse-shared-gpu"] if shared else [])
     if launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
@@ -204,12 +205,11 @@ def test_bench_refuses_ranks_sharing_a_gpu_without_the_rehearsal_flag(launcher):
 
 
 def test_bench_single_rank_line_checks(oracle):
-    """bench.py at N = 1 (plain `python bench.py`, as the driver runs it) at
-    config 2's 4096 chunks: parity against the reference's golden digests and
+    """bench.py --full at N = 1 at config 2's 4096 chunks: parity against the reference's golden digests and
     checksum, and the device-resident verify leg flags exactly the planted
     mismatches (the fused compare of util.c:311-313)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--chunks", "4096", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--chunks", "4096", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline", "--no-host-path", "--power-s", "0"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -231,8 +231,39 @@ def test_bench_single_rank_line_checks(oracle):
     _check_sample(line, 1, 4096, oracle)
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_digests(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its steps and
+    prints the line, nothing else: the legs of --full are null.  With
+    --dump-outputs it also writes the last timed step's digests, float32
+    [chunks, 20] in global chunk order -- here config 2's 4096 chunks, every
+    one equal to the reference's golden digest."""
+    import numpy as np
+    from conftest import read_pairs
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--chunks", "4096",
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 2**30 - 4096 * CHUNK) < 1e-3 * 4096 * CHUNK
+    for leg in ("clock", "power", "cpu_baseline", "verify_dev", "host_path", "parity_first_4096_vs_golden",
+                "parity_all_vs_golden", "digest_sample", "digests_sha1"):
+        assert line[leg] is None, leg
+    assert set(line["phases_s"]) == {"init_s", "fill_s", "warmup_and_timed_s", "gather_and_parity_s", "dump_outputs_s"}
+    assert line["roofline"]["kernel_ms"] > 0 and line["per_gpu"][0]["chunk_range"] == [0, 4096]
+    assert line["dumped_outputs"] == ["digests"] and os.listdir(tmp_path / "out") == ["digests.npy"]
+    d = np.load(tmp_path / "out" / "digests.npy")
+    assert d.dtype == np.float32 and d.shape == (4096, 20)
+    want = {int(i): h for i, h in read_pairs("synth4096.txt")}
+    assert len(want) == 4096 and all(d[i].astype(np.uint8).tobytes().hex() == want[i] for i in range(4096))
+
+
 def test_bench_host_path_leg_explains_itself(oracle):
-    """Config 5 in the N = 1 line (a 1 GiB image here): each pipeline rate is
+    """Config 5 in the N = 1 line of --full (a 1 GiB image here): each pipeline rate is
     the median of 5 steady-state runs after a first one, every run listed
     with its phase split (providing the input on the host vs blocked on the
     GPU lane, page registration), machine CPU load and cgroup throttling;
@@ -242,7 +273,7 @@ def test_bench_host_path_leg_explains_itself(oracle):
     (util.c:275's 1484-byte memcpys) on one and on four receive threads --
     every digest and verdict right."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--chunks", "4096", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--chunks", "4096", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline", "--host-gib", "1", "--power-s", "0", "--no-clock"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -41,25 +41,25 @@ for step in "$@"; do
       # a subset of the gpu suite: pytest:<-k expression>
       run "pytest_${step#pytest:}" 600 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
         -p no:cacheprovider -k "${step#pytest:}" ;;
-    bench) run bench 600 python3 bench.py ;;
+    bench) run bench 600 python3 bench.py --full ;;
     driver_bench)
       # the driver's exact N=1 command (BENCH_rNN.json), timed from outside as well
       t0=$(date +%s%N)
-      run driver_bench 600 python3 bench.py --gpus 1 --steps 20 --warmup 5
+      run driver_bench 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5
       echo "driver_bench outer wall ms: $(( ($(date +%s%N) - t0) / 1000000 ))" | tee -a "$OUT/session.log" ;;
     bench2)
       # two default runs back to back on one box (within-box repeatability of the line)
-      run bench_a 600 python3 bench.py && run bench_b 600 python3 bench.py ;;
+      run bench_a 600 python3 bench.py --full && run bench_b 600 python3 bench.py --full ;;
     bench_rings)
-      for r in 2 3 4; do run bench_ring$r 300 python3 bench.py --ring $r --steps 10 --no-cpu-baseline; done ;;
+      for r in 2 3 4; do run bench_ring$r 300 python3 bench.py --full --ring $r --steps 10 --no-cpu-baseline; done ;;
     prof)
       # same process: the bench line (prof.log) and the rocprof kernel stats
       mkdir -p "$OUT/prof"
       run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench \
-        -- python3 "$ROOT/bench.py" --steps 20 --no-cpu-baseline --no-host-path --no-clock --power-s 0 ;;
+        -- python3 "$ROOT/bench.py" --full --steps 20 --no-cpu-baseline --no-host-path --no-clock --power-s 0 ;;
     pmc)
       mkdir -p "$OUT/pmc"
-      PB="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --no-clock --power-s 0"
+      PB="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --no-clock --power-s 0"
       run pmc_fetch 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc" -o fetch -- $PB
       run pmc_rdreq 600 rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$OUT/pmc" -o rdreq -- $PB
       run pmc_valu 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc" -o valu -- $PB
@@ -73,17 +73,17 @@ for step in "$@"; do
       for rep in 1 2; do
         for n in default maxilp iterilp maxmem bias0; do
           d="$ROOT/build_variants/$n"
-          run "libvar_${n}_$rep" 300 env BT_SHA1_LIB="$d/libbtsha1.so" python3 bench.py --steps 10 --no-cpu-baseline
+          run "libvar_${n}_$rep" 300 env BT_SHA1_LIB="$d/libbtsha1.so" python3 bench.py --full --steps 10 --no-cpu-baseline
         done
       done ;;
     dist2)
       # the driver's N>1 launch line, rehearsed with 2 and 4 ranks sharing this box's one GPU
       run dist2 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29531 bench.py --gpus 2 --chunks 16384 --steps 5 --warmup 2 --rehearse-shared-gpu
+        --master-port 29531 bench.py --full --gpus 2 --chunks 16384 --steps 5 --warmup 2 --rehearse-shared-gpu
       run dist4 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-        --master-port 29532 bench.py --gpus 4 --chunks 8192 --steps 5 --warmup 2 --rehearse-shared-gpu
+        --master-port 29532 bench.py --full --gpus 4 --chunks 8192 --steps 5 --warmup 2 --rehearse-shared-gpu
       # the driver's other N > 1 shape: no launcher, bench.py starts the ranks itself
-      run dist2_self 600 python3 bench.py --gpus 2 --chunks 16384 --steps 5 --warmup 2 --rehearse-shared-gpu ;;
+      run dist2_self 600 python3 bench.py --full --gpus 2 --chunks 16384 --steps 5 --warmup 2 --rehearse-shared-gpu ;;
     pairing)
       run pairing 300 "$ROOT/tools/ubench/pairing"
       mkdir -p "$OUT/pairing_pmc"
@@ -103,23 +103,23 @@ for step in "$@"; do
     variants)
       for v in "2 1 0" "3 1 0" "4 1 0" "2 2 0" "2 1 1" "3 1 1" "2 2 1"; do
         set -- $v
-        run "var_$1$2$3" 300 python3 bench.py --ring $1 --lines $2 --nt $3 --steps 5 --no-cpu-baseline
+        run "var_$1$2$3" 300 python3 bench.py --full --ring $1 --lines $2 --nt $3 --steps 5 --no-cpu-baseline
       done ;;
     pitches)
       for p in 524416 524544 528384 589824; do
-        run "pitch_$p" 300 python3 bench.py --pitch $p --steps 5 --no-cpu-baseline
+        run "pitch_$p" 300 python3 bench.py --full --pitch $p --steps 5 --no-cpu-baseline
       done ;;
     occupancy)
-      run occ_262144 300 python3 bench.py --ring 2 --chunks 262144 --steps 5 --no-cpu-baseline
-      run occ_393216 300 python3 bench.py --ring 2 --chunks 393216 --steps 5 --no-cpu-baseline ;;
+      run occ_262144 300 python3 bench.py --full --ring 2 --chunks 262144 --steps 5 --no-cpu-baseline
+      run occ_393216 300 python3 bench.py --full --ring 2 --chunks 393216 --steps 5 --no-cpu-baseline ;;
     occupancy2)
       # round 4: parallelism beyond the workload's 2 waves/SIMD, same box, alternating:
       # one launch of 131072 chunks, one of 262144, two concurrent processes of 131072
-      B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-path"
+      B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-path"
       for rep in 1 2; do
         run "occ_n1_$rep" 200 $B && run "occ_n1_262k_$rep" 200 $B --chunks 262144 && \
         run "occ_n2_$rep" 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-          --master-port 2955$rep bench.py --gpus 2 --steps 20 --warmup 5 --rehearse-shared-gpu || exit 1
+          --master-port 2955$rep bench.py --full --gpus 2 --steps 20 --warmup 5 --rehearse-shared-gpu || exit 1
       done ;;
     counters) run counters 120 rocprofv3 -L ;;
     residency) run residency 300 "$ROOT/tools/ubench/residency" ;;
@@ -140,14 +140,14 @@ for step in "$@"; do
       for rep in 1 2; do
         for v in "3 1 0" "2 1 0" "4 1 0" "2 2 0" "10 1 0"; do
           set -- $v
-          run "v597_$1$2$3_$rep" 300 python3 bench.py --ring $1 --lines $2 --nt $3 --steps 20 --no-cpu-baseline
+          run "v597_$1$2$3_$rep" 300 python3 bench.py --full --ring $1 --lines $2 --nt $3 --steps 20 --no-cpu-baseline
         done
       done ;;
     lds_ab)
       for rep in 1 2; do
-        run "ab_ring3_$rep" 300 python3 bench.py --ring 3 --steps 20 --no-cpu-baseline
-        run "ab_lds_$rep" 300 python3 bench.py --ring 10 --steps 20 --no-cpu-baseline
-        run "ab_ldsnt_$rep" 300 python3 bench.py --ring 10 --nt 1 --steps 20 --no-cpu-baseline
+        run "ab_ring3_$rep" 300 python3 bench.py --full --ring 3 --steps 20 --no-cpu-baseline
+        run "ab_lds_$rep" 300 python3 bench.py --full --ring 10 --steps 20 --no-cpu-baseline
+        run "ab_ldsnt_$rep" 300 python3 bench.py --full --ring 10 --nt 1 --steps 20 --no-cpu-baseline
       done ;;
     power_valu)
       sampler "$OUT/power_valu_samples.log" 50 &
@@ -157,7 +157,7 @@ for step in "$@"; do
     power_lds)
       sampler "$OUT/power_lds_samples.log" 40 &
       sp=$!
-      run power_lds 300 python3 bench.py --ring 10 --steps 1500 --warmup 3 --no-cpu-baseline
+      run power_lds 300 python3 bench.py --full --ring 10 --steps 1500 --warmup 3 --no-cpu-baseline
       wait $sp ;;
     power_stream2)
       sampler "$OUT/power_stream2_samples.log" 90 &
@@ -171,7 +171,7 @@ for step in "$@"; do
       for rep in 1 2; do
         for v in "3 1 0" "2 1 0" "4 1 0" "2 2 0" "10 1 0" "10 1 1"; do
           set -- $v
-          run "energy_$1$2$3_$rep" 300 python3 bench.py --ring $1 --lines $2 --nt $3 --steps 20 \
+          run "energy_$1$2$3_$rep" 300 python3 bench.py --full --ring $1 --lines $2 --nt $3 --steps 20 \
             --no-cpu-baseline --no-host-path --power-s 4
         done
       done ;;
@@ -180,7 +180,7 @@ for step in "$@"; do
       ( for i in $(seq 1 12); do date +%T; timeout 10 amd-smi metric -g 0 -p -c 2>&1
           timeout 10 rocm-smi --showpower --showgpuclocks 2>&1; sleep 2; done ) > "$OUT/power_samples.log" 2>&1 &
       sp=$!
-      run power_bench 300 python3 bench.py --steps 1500 --warmup 3 --no-cpu-baseline
+      run power_bench 300 python3 bench.py --full --steps 1500 --warmup 3 --no-cpu-baseline
       wait $sp ;;
     stream)
       python3 -c "import lzma; open('/tmp/C.tar','wb').write(lzma.decompress(open('tests/golden/C.tar.xz','rb').read()))"
