@@ -71,6 +71,7 @@ _sig("bt_sha1_set_variant", ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_i
 _sig("bt_sha1_set_latency_batch", _u64, _u64)
 _sig("bt_sha1_chunks_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp)
 _sig("bt_sha1_verify_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp)
+_sig("bt_sha1_column_dev", ctypes.c_int, _vp, _u64, _u64, _u64, ctypes.c_int, _vp, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_ragged_dev", ctypes.c_int, _vp, _vp, _vp, _u64, _vp, _vp)
 _sig("bt_sha1_fill_synthetic", ctypes.c_int, _vp, _u64, _u64, _u64, _vp)
 _sig("bt_sha1_chunks_host", _i64, _vp, _u64, _u64, _vp)
@@ -202,6 +203,19 @@ def chunks_dev(d_in, n, chunk_len, pitch, d_digests, stream=None):
 def verify_dev(d_in, n, chunk_len, pitch, d_expected, d_ok, d_digests=None, stream=None):
     _check(lib.bt_sha1_verify_dev(d_in, n, chunk_len, pitch, d_expected, d_ok, d_digests, stream),
            "bt_sha1_verify_dev")
+
+
+COLUMN_FIRST, COLUMN_MIDDLE, COLUMN_LAST = 0, 1, 2
+
+
+def column_dev(d_col, n, pitch, width, part, d_state, msg_len=0, d_digests=None, d_expected=None, d_ok=None,
+               stream=None):
+    """One launch of the latency kernel's column form (diagnostic): `width`
+    bytes of each of n chunks at d_col + i*pitch, chaining state in d_state
+    (word k of chunk i at d_state[k*n + i]); COLUMN_LAST finishes a message of
+    msg_len bytes into d_digests and / or the fused compare's d_ok."""
+    _check(lib.bt_sha1_column_dev(d_col, n, pitch, width, part, d_state, msg_len, d_digests, d_expected, d_ok,
+                                  stream), "bt_sha1_column_dev")
 
 
 def ragged_dev(d_base, d_offsets, d_lens, n, d_digests, stream=None):

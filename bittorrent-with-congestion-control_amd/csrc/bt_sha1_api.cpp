@@ -967,6 +967,20 @@ uint32_t columns() {
   }();
   return v;
 }
+// Columns a chunk of chunk_len bytes is split into, by the pipelines' tail
+// and the verifier's batches alike: columns(), halved until the chunk divides
+// into whole 64-byte blocks; 0 (no split: whole-chunk launches) when there is
+// no such count, the chunk is under kColumnMinChunk, or the column -- dense,
+// pitch == width = chunk_len / parts -- is one btsha1_launch_column refuses:
+// no 64-byte multiple, a pitch off 16 bytes, or 64 * pitch >= 4 GiB (a column
+// of 64 MiB or more: a workgroup's 64 rows are addressed by 32-bit offsets).
+uint32_t split_columns(uint64_t chunk_len) {
+  uint32_t parts = columns();
+  while (parts >= 2 && chunk_len % (64ull * parts)) parts /= 2;
+  if (parts < 2 || chunk_len < kColumnMinChunk) return 0;
+  const uint64_t width = chunk_len / parts;
+  return width && !(width & 63u) && !(width & 15u) && 64ull * width < (1ull << 32) ? parts : 0;
+}
 std::atomic<int> g_pageable_feed{-1};  // BT_SHA1_PAGEABLE_REGISTER / _STAGE; -1: not read yet
 int pageable_feed() {
   int v = g_pageable_feed.load();
@@ -1039,8 +1053,7 @@ int64_t chunks_host_on(int dev, const uint8_t *h_in, uint64_t total, uint64_t ch
   } sp;
   const double t_lock0 = now_s();
   {
-    uint32_t parts = columns();
-    while (parts >= 2 && chunk_len % (64ull * parts)) parts /= 2;
+    const uint32_t parts = split_columns(chunk_len);
     // about one batch of this feed, never more than a kept lane holds
     // (1 GiB: the idle lane carries the columns, and a staged lane is never
     // shrunk after the call)
@@ -1058,7 +1071,7 @@ int64_t chunks_host_on(int dev, const uint8_t *h_in, uint64_t total, uint64_t ch
       lo = (base + c0 * chunk_len) & ~(uintptr_t)(kPage - 1);
       hi = (base + c1 * chunk_len + kPage - 1) & ~(uintptr_t)(kPage - 1);
     }
-    if (parts >= 2 && chunk_len >= kColumnMinChunk && c1 > c0 + 1 && (c1 - c0) * chunk_len >= column_min_bytes() &&
+    if (parts && c1 > c0 + 1 && (c1 - c0) * chunk_len >= column_min_bytes() &&
         !c->h_cdig.ensure(20 * (nchunks - t0 + 3)) && !c->h_cleft.ensure(3 * chunk_len) &&
         !c->d_cstate.ensure(20 * (c1 - c0))) {
       bool ok = true;
@@ -1665,6 +1678,32 @@ int bt_sha1_verify_dev(const void *d_in, uint64_t n, uint64_t chunk_len, uint64_
   return 0;
 }
 
+int bt_sha1_column_dev(const void *d_col, uint64_t n, uint64_t pitch, uint64_t width, int part, uint32_t *d_state,
+                       uint64_t msg_len, uint8_t *d_digests, const uint8_t *d_expected, uint8_t *d_ok, void *stream) {
+  if (n == 0) return 0;
+  if (!d_col || !d_state) {
+    set_err("null pointer");
+    return -1;
+  }
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  DevCtx *c = ctx_for(dev);
+  if (!c) return -1;
+  hipStream_t st = pick_stream(stream);
+  // The launcher takes 32-bit pitch and width: what does not fit is refused
+  // here, like its own 64*pitch < 4 GiB, not truncated into something valid.
+  const hipError_t e = pitch >> 32 || width >> 32
+                           ? hipErrorInvalidValue
+                           : btsha1_launch_column(d_col, n, (uint32_t)pitch, (uint32_t)width, part, d_state, msg_len,
+                                                  d_digests, st, d_expected, d_ok);
+  if (e != hipSuccess) {
+    set_err("column launch (part %d, n %llu, width %llu, pitch %llu) refused: %s", part, (unsigned long long)n,
+            (unsigned long long)width, (unsigned long long)pitch, hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
 int bt_sha1_ragged_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
                        uint8_t *d_digests, void *stream) {
   if (n == 0) return 0;
@@ -2068,10 +2107,8 @@ int v_harvest(bt_sha1_verifier *v, VBatch &b) {
 // column's hash (~0.9 ms), not one whole chunk's (~6.7 ms), after its last
 // byte crossed PCIe.
 uint32_t v_columns(uint64_t chunk_len, uint64_t rows) {
-  uint32_t parts = columns();
-  while (parts >= 2 && chunk_len % (64ull * parts)) parts /= 2;
-  return parts >= 2 && chunk_len >= kColumnMinChunk && rows >= 2 && rows * chunk_len >= column_min_bytes() ? parts
-                                                                                                            : 0;
+  const uint32_t parts = split_columns(chunk_len);
+  return parts && rows >= 2 && rows * chunk_len >= column_min_bytes() ? parts : 0;
 }
 
 int v_launch_columns(bt_sha1_verifier *v, VBatch &b, uint32_t parts) {

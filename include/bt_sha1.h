@@ -115,6 +115,23 @@ int bt_sha1_debug_barrier_stats(uint64_t out[3], int reset);
  * -1 for a negative device.  Scans the whole staging buffer: a test hook, not
  * for hot loops. */
 int64_t bt_sha1_debug_dropin_residue(int device);
+/* Diagnostic: ONE launch of the latency kernel's column form, which the host
+ * pipelines' column-split tail and the verifier's split batches chain per
+ * chunk (test hook: they reach it only with chunks of 64 KiB or more).
+ * Column `part` (0 first, 1 middle, 2 last) of n chunks: chunk i's column is
+ * `width` bytes (a 64-byte multiple) at d_col + i*pitch (16-byte aligned;
+ * pitch >= width, a 16-byte multiple, 64*pitch < 4 GiB).  d_state (5*n
+ * uint32, device memory) carries each chunk's chaining state from column to
+ * column, word k of chunk i at d_state[k*n + i]: the first part starts from
+ * the SHA-1 IV and writes it, a middle part advances it, the last part reads
+ * it, appends the padding of a msg_len-byte message (the bytes of all the
+ * parts) and writes digest i to d_digests + 20*i (4-byte aligned) -- and with
+ * d_ok (last part only) d_ok[i] = digest i == d_expected[20*i ..], where
+ * d_digests may be NULL.  Returns -1, with nothing launched, for arguments
+ * the launcher refuses. */
+int bt_sha1_column_dev(const void *d_col, uint64_t n, uint64_t pitch, uint64_t width, int part,
+                       uint32_t *d_state, uint64_t msg_len, uint8_t *d_digests,
+                       const uint8_t *d_expected, uint8_t *d_ok, void *stream);
 
 /* ---- device-resident batches (the hot path) ---------------------------- */
 /* n chunks of chunk_len bytes, chunk i at d_in + i*pitch (pitch >= chunk_len).

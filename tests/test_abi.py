@@ -42,6 +42,29 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+@pytest.mark.parametrize("variant", ["dbgbar", "experiments"])
+def test_variant_libraries_export_every_declared_symbol(variant):
+    """The diagnostic builds the GPU tests load in place of the product
+    (BT_SHA1_LIB) carry the whole C-ABI too, bt_sha1_column_dev included."""
+    lib = os.path.join(REPO, "build_variants", variant, "libbtsha1.so")
+    assert os.path.exists(lib), f"run make {variant} first"
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    names = declared_functions()
+    assert "bt_sha1_column_dev" in names
+    assert not names - exported, names - exported
+
+
+def test_column_dev_refuses_null_buffers_before_any_device_call():
+    """bt_sha1_column_dev: no chunks is no work, null buffers are -1 with a
+    message -- both before a device is looked for, so they hold without one."""
+    bt = load_btsha1()
+    assert bt.lib.bt_sha1_column_dev(None, 0, 64, 64, 0, None, 0, None, None, None, None) == 0
+    for d_col, d_state in ((None, 4096), (4096, None)):
+        assert bt.lib.bt_sha1_column_dev(d_col, 1, 64, 64, 0, d_state, 0, None, None, None, None) == -1
+        assert "null pointer" in bt.last_error()
+
+
 def test_library_is_gfx950_code_object():
     blob = open(LIB, "rb").read()
     assert b"amdgcn-amd-amdhsa--gfx950" in blob

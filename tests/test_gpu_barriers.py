@@ -176,5 +176,89 @@ def test_barrier_accounting_build_matches_invariant():
     assert not bad, bad
 
 
+def _child_columns():
+    import ctypes
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    sys.path.insert(0, PKG)
+    import btsha1 as bt
+    import column_cases as cc
+    import py_oracle as orc
+
+    assert torch.cuda.is_available()
+    assert os.path.samefile(bt.LIB_PATH, DBG_LIB), bt.LIB_PATH
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    bt.debug_barrier_stats(reset=True)
+    results = []
+
+    def record(name, want, problems):
+        got = bt.debug_barrier_stats(reset=True)
+        results.append({"case": name, "want": list(want), "got": list(got), "digests_ok": not problems,
+                        "problems": problems})
+
+    # ---- one launch at a time: the small shapes first, so a miscount shows at 6 MiB, not at 1 GiB
+    for case in cc.cases(cus):
+        cc.run_case(bt, torch, orc, case,
+                    lambda label, n, width, part, bad: record(label, cc.barrier_want(n, width, part, cus), bad))
+
+    # ---- whole split batches through the public verifier
+    def verifier(name, chunk_len, batch):
+        parts, width = 8, chunk_len // 8
+        assert chunk_len % (64 * parts) == 0
+        img = bytearray(batch * chunk_len)
+        view = np.frombuffer(img, dtype=np.uint64)
+        view[:] = np.arange(view.size, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(chunk_len)
+        ref = orc.hash_chunks(img, chunk_len, nthreads=8)
+        v = bt.Verifier(chunk_len=chunk_len, batch=batch, nstreams=2)
+        want = []
+        for k in range(batch):
+            p = v.slot()
+            if k % 211 == 5:  # an aborted download: hashed with the batch, no verdict
+                v.release(p)
+                continue
+            ctypes.memmove(p, (ctypes.c_uint8 * chunk_len).from_buffer(img, k * chunk_len), chunk_len)
+            v.commit(p, ref[k] if k % 97 else bytes(20), tag=k)
+            want.append((k, k % 97 != 0, ref[k]))
+        got = v.drain()
+        v.close()
+        problems = [] if got == want else [f"{len(got)} verdicts for {len(want)} chunks, "
+                                           f"{sum(a != b for a, b in zip(got, want))} differ"]
+        grid = (batch + 63) // 64  # released slots are rows of the batch like any other
+        slots = 3 if grid > cus else 2
+        nbs = [width // 64] * (parts - 1) + [width // 64 + 1]
+        record(name, (2 * grid * parts, sum(2 * grid * (nb + slots - 1) for nb in nbs)), problems)
+
+    verifier("verifier 3-slot: 64 KiB x (64 CUs + 64)", 64 << 10, 64 * cus + 64)
+    verifier("verifier 16 MiB x 4", 16 << 20, 4)
+    verifier("verifier (4 MiB + 512) x 6, nblocks % 4 == 1", (4 << 20) + 512, 6)
+    print("BARRIER_RESULTS " + json.dumps(results), flush=True)
+
+
+def _run_child(mode, env, timeout):
+    assert os.path.exists(DBG_LIB), "build_variants/dbgbar/libbtsha1.so missing: run `make dbgbar` first"
+    env = dict(os.environ, BT_SHA1_LIB=DBG_LIB, HSA_ENABLE_IPC_MODE_LEGACY="0", **env)
+    r = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), mode], cwd=REPO, env=env,
+                       capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("BARRIER_RESULTS ")]
+    assert len(line) == 1, r.stdout[-2000:]
+    return json.loads(line[0].split(" ", 1)[1])
+
+
+def test_column_forms_match_the_barrier_invariant():
+    results = _run_child("child-columns", {"BT_SHA1_COLUMN_MIN_MB": "0"}, 300)
+    for c in results:
+        print(c["case"], "want", c["want"], "got", c["got"], c["problems"])
+    # cases a to d: 4 + 4 + 5 + 5 + 4 launches; three verifier batches
+    assert len(results) == 22 + 3
+    assert any("3-slot" in c["case"] and "MIDDLE" in c["case"] for c in results)
+    bad = [c for c in results if not c["digests_ok"] or c["got"][2] != 0 or c["got"][:2] != c["want"]]
+    assert not bad, bad
+
+
 if __name__ == "__main__" and sys.argv[1:] == ["child"]:
     _child()
+if __name__ == "__main__" and sys.argv[1:] == ["child-columns"]:
+    _child_columns()

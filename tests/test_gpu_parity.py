@@ -773,6 +773,73 @@ def test_column_split_tail_at_full_size(bt, oracle):
             bt.set_pageable_feed(prev)
 
 
+_LARGE_CHUNK_CHILD = (
+    "import sys, numpy as np; sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2]);"
+    "import btsha1 as bt, py_oracle as o;"
+    "cl, nfull, extra = int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]); n = nfull * cl + extra;"
+    "raw = np.empty(n + 8 - n % 8, dtype=np.uint8);"
+    "raw.view(np.uint64)[:] = np.arange(raw.size // 8, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(cl);"
+    "d = raw[:n]; w = b''.join(o.hash_chunks(d, cl, nthreads=8));\n"
+    "def run(tag):\n"
+    "    try:\n"
+    "        got = bt.chunks_host_addr(d.ctypes.data, n, chunk_len=cl)\n"
+    "    except bt.BtSha1Error as e:\n"
+    "        print(tag, 'error', 'x', 'x', 'x', str(e).replace(' ', '_')); return\n"
+    "    s = bt.pipeline_stats()\n"
+    "    print(tag, 'exact' if got == w else 'WRONG', s['feed'], s['column_chunks'], s['chunks'], '-')\n"
+    "for tag in sys.argv[6].split(','):\n"
+    "    if tag == 'pinned':\n"
+    "        bt.host_register(d.ctypes.data, n)\n"
+    "        try:\n"
+    "            run(tag)\n"
+    "        finally:\n"
+    "            bt.host_unregister(d.ctypes.data)\n"
+    "    elif tag == 'stage':\n"
+    "        bt.set_pageable_feed('stage'); run(tag); bt.set_pageable_feed('register')\n"
+    "    else:\n"
+    "        run(tag)\n")
+
+
+def _large_chunk_child(env, chunk_len, nfull, extra, feeds, timeout=180):
+    """{feed tag: (outcome, feed, column_chunks, chunks, error)} of bt_sha1_chunks_host in a child process."""
+    r = subprocess.run([sys.executable, "-c", _LARGE_CHUNK_CHILD, PKG, os.path.join(REPO, "oracle"), str(chunk_len),
+                        str(nfull), str(extra), feeds], capture_output=True, text=True,
+                       env=dict(os.environ, **env), timeout=timeout)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
+    print(r.stdout)
+    rows = [l.split() for l in r.stdout.splitlines()]
+    return {t[0]: (t[1], t[2], t[3], t[4], t[5]) for t in rows}
+
+
+# (full chunks, feed the pageable image takes): 36 MiB stays under the 64 MiB
+# a pageable image needs to be page-locked in place, 68 MiB is over it
+@pytest.mark.parametrize("nfull,pageable_feed", [(9, "staged"), (17, "registered")])
+def test_column_split_tail_at_4_mib_chunks(nfull, pageable_feed):
+    """The column-split tail at chunks eight times the usual size: 4 MiB
+    chunks (512 KiB columns of 8192 blocks) and 333 more bytes, caller-pinned
+    (direct DMA), pageable and with the staging feed forced; every digest
+    equals the oracle's and each run took the split."""
+    got = _large_chunk_child({"BT_SHA1_COLUMN_MIN_MB": "0"}, 4 << 20, nfull, 333, "pinned,pageable,stage")
+    assert set(got) == {"pinned", "pageable", "stage"}
+    for tag, feed in (("pinned", "direct"), ("pageable", pageable_feed), ("stage", "staged")):
+        outcome, fed, cols, chunks, err = got[tag]
+        assert (outcome, fed, int(chunks)) == ("exact", feed, nfull + 1), (tag, got[tag])
+        assert int(cols) > 0, (tag, got[tag])
+
+
+def test_column_split_skipped_when_the_column_is_too_wide():
+    """A chunk whose column would be 64 MiB or more (64 * pitch >= 4 GiB, which
+    the column launcher refuses) is hashed whole, not split: 3 pinned chunks
+    of 128 MiB with BT_SHA1_COLUMNS=2, where chunks 1 and 2 would form the
+    split at 64 MiB columns.  Before the split checked the width this call
+    failed with hipErrorInvalidValue from btsha1_launch_column."""
+    got = _large_chunk_child({"BT_SHA1_COLUMNS": "2", "BT_SHA1_COLUMN_MIN_MB": "0"}, 128 << 20, 3, 0, "pinned",
+                             timeout=300)
+    outcome, fed, cols, chunks, err = got["pinned"]
+    assert outcome != "error", err
+    assert (outcome, fed, int(cols), int(chunks)) == ("exact", "direct", 0, 3), got
+
+
 def test_registered_host_image_direct_dma(bt, oracle):
     import numpy as np
     data = np.frombuffer(bytes(oracle.fill_synthetic(9 * CHUNK + 777, 5, 0xD1A), ), dtype=np.uint8).copy()
