@@ -26,21 +26,27 @@ all: lib tools oracle dropin asan dbgbar experiments
 
 lib: $(LIB)
 
-$(PKG)/build/sha1_kernels.o: $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(PKG)/build/bt_sha1_api.o: $(CSRC)/bt_sha1_api.cpp $(CSRC)/sha1_launch.h include/bt_sha1.h include/sha.h include/chunk.h \
-                           $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_SRC_ID='"$(SRC_ID)"' -c $< -o $@
-
-$(PKG)/build/bt_chunks.o: $(CSRC)/bt_chunks.cpp include/bt_sha1.h include/chunk.h
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIB): $(PKG)/build/sha1_kernels.o $(PKG)/build/bt_sha1_api.o $(PKG)/build/bt_chunks.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -Wl,-soname,libbtsha1.so
+# The host runtime: bt_runtime carries the source id and is compiled for every
+# build of the library; the others do not depend on the build, so every
+# variant but asan (which instruments all host code) links the product's.
+HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_chunks
+HOSTOBJ  := $(HOST:%=$(PKG)/build/%.o)
+KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h
+HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/sha.h include/chunk.h
+SONAME   := -Wl,-soname,libbtsha1.so
+# One build of the library: $(call libbtsha1,object dir,library,kernel flags,
+# host flags,source id suffix,host objects besides bt_runtime.o,link flags)
+define libbtsha1
+$(1)/sha1_kernels.o: $$(KDEPS)
+	@mkdir -p $$(dir $$@)
+	$$(HIPCC) $$(HIPFLAGS) $(3) -c $$< -o $$@
+$(1)/%.o: $$(CSRC)/%.cpp $$(HDRS) $$(KDEPS)
+	@mkdir -p $$(dir $$@)
+	$$(HIPCC) $$(HIPFLAGS) $(4) -DBT_SHA1_SRC_ID='"$$(SRC_ID)$(5)"' -c $$< -o $$@
+$(2): $(1)/sha1_kernels.o $(1)/bt_runtime.o $(6)
+	$$(HIPCC) --offload-arch=$$(ARCH) -shared -fPIC -o $$@ $$^ $(7)
+endef
+$(eval $(call libbtsha1,$(PKG)/build,$(LIB),,,,$(HOSTOBJ),$(SONAME)))
 
 # Host-side callers above the C-ABI (C, like the reference).
 tools: $(BIN)/make-chunks $(BIN)/verify-stream
@@ -91,15 +97,9 @@ ASANFLAGS := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xa
 asan: $(ASANDIR)/host_stress
 
 # Like every build but `experiments`, the kernels carry only the default hot
-# kernel.  Each diagnostic build compiles the API object with its own suffixed
+# kernel.  Each diagnostic build compiles bt_runtime with its own suffixed
 # source id, so bench.py never credits it with the product's PMC traffic.
-$(ASANDIR)/libbtsha1.so: $(CSRC)/bt_sha1_api.cpp $(CSRC)/bt_chunks.cpp $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h \
-                        $(CSRC)/sha1_launch.h include/bt_sha1.h
-	@mkdir -p $(ASANDIR)
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/sha1_kernels.hip -o $(ASANDIR)/sha1_kernels.o
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_SRC_ID='"$(SRC_ID)-asan"' -gline-tables-only $(ASANFLAGS) -c $(CSRC)/bt_sha1_api.cpp -o $(ASANDIR)/bt_sha1_api.o
-	$(HIPCC) $(HIPFLAGS) -gline-tables-only $(ASANFLAGS) -c $(CSRC)/bt_chunks.cpp -o $(ASANDIR)/bt_chunks.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(ASANDIR)/sha1_kernels.o $(ASANDIR)/bt_sha1_api.o $(ASANDIR)/bt_chunks.o
+$(eval $(call libbtsha1,$(ASANDIR),$(ASANDIR)/libbtsha1.so,,-gline-tables-only $(ASANFLAGS),-asan,$(HOST:%=$(ASANDIR)/%.o),))
 
 $(ASANDIR)/host_stress: tests/native/host_stress.c $(ASANDIR)/libbtsha1.so
 	/opt/rocm/llvm/bin/clang -gline-tables-only -O1 -fsanitize=address,undefined -shared-libasan -fno-omit-frame-pointer -Iinclude -o $@ $< \
@@ -108,16 +108,11 @@ $(ASANDIR)/host_stress: tests/native/host_stress.c $(ASANDIR)/libbtsha1.so
 # Barrier-accounting build: the latency / chain / ragged-latency kernels count
 # the s_barriers each wave executes and check them against the invariant they
 # rely on (sha1_kernels.hip, "Barrier accounting"); bt_sha1_debug_barrier_stats
-# reads the tallies.  Same API objects, only the kernel object differs.  Run by
+# reads the tallies.  Same host objects, only the kernel object differs.  Run by
 # tests/test_gpu_barriers.py in a child process (BT_SHA1_LIB points at it).
 DBGDIR   := build_variants/dbgbar
 dbgbar: $(DBGDIR)/libbtsha1.so
-$(DBGDIR)/libbtsha1.so: $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/bt_sha1_api.cpp \
-                        include/bt_sha1.h $(PKG)/build/bt_chunks.o
-	@mkdir -p $(DBGDIR)
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_DEBUG_BARRIERS -c $< -o $(DBGDIR)/sha1_kernels.o
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_SRC_ID='"$(SRC_ID)-dbgbar"' -c $(CSRC)/bt_sha1_api.cpp -o $(DBGDIR)/bt_sha1_api.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(DBGDIR)/sha1_kernels.o $(DBGDIR)/bt_sha1_api.o $(PKG)/build/bt_chunks.o -Wl,-soname,libbtsha1.so
+$(eval $(call libbtsha1,$(DBGDIR),$(DBGDIR)/libbtsha1.so,-DBT_SHA1_DEBUG_BARRIERS,,-dbgbar,$(HOSTOBJ),$(SONAME)))
 
 # Experiments build: the hot-kernel variants measured and rejected (ring depth
 # 2 / 4, two-line slots, non-temporal loads, LDS-DMA staging)
@@ -126,12 +121,7 @@ $(DBGDIR)/libbtsha1.so: $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/s
 # by tests/test_gpu_variants.py in a child process and by bench.py --ring.
 EXPDIR   := build_variants/experiments
 experiments: $(EXPDIR)/libbtsha1.so
-$(EXPDIR)/libbtsha1.so: $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/bt_sha1_api.cpp \
-                        include/bt_sha1.h $(PKG)/build/bt_chunks.o
-	@mkdir -p $(EXPDIR)
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_EXPERIMENTS -c $< -o $(EXPDIR)/sha1_kernels.o
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_SRC_ID='"$(SRC_ID)-exp"' -c $(CSRC)/bt_sha1_api.cpp -o $(EXPDIR)/bt_sha1_api.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(EXPDIR)/sha1_kernels.o $(EXPDIR)/bt_sha1_api.o $(PKG)/build/bt_chunks.o -Wl,-soname,libbtsha1.so
+$(eval $(call libbtsha1,$(EXPDIR),$(EXPDIR)/libbtsha1.so,-DBT_SHA1_EXPERIMENTS,,-exp,$(HOSTOBJ),$(SONAME)))
 
 # Scheduler-strategy builds of the library (experiment in profiles/r01/experiments.md;
 # tools/gpu_session.sh libvariants benches each).  Not part of the product.
@@ -142,11 +132,7 @@ SCHED_maxmem  := -mllvm -amdgpu-sched-strategy=max-memory-clause
 SCHED_bias0   := -mllvm -amdgpu-schedule-metric-bias=0
 SCHED_NAMES   := default maxilp iterilp maxmem bias0
 sched_variants: $(foreach v,$(SCHED_NAMES),build_variants/$(v)/libbtsha1.so)
-build_variants/%/libbtsha1.so: $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/bt_sha1_api.cpp $(PKG)/build/bt_chunks.o
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) $(SCHED_$*) -c $< -o $(dir $@)sha1_kernels.o
-	$(HIPCC) $(HIPFLAGS) -DBT_SHA1_SRC_ID='"$(SRC_ID)-sched-$*"' -c $(CSRC)/bt_sha1_api.cpp -o $(dir $@)bt_sha1_api.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(dir $@)sha1_kernels.o $(dir $@)bt_sha1_api.o $(PKG)/build/bt_chunks.o -Wl,-soname,libbtsha1.so
+$(foreach v,$(SCHED_NAMES),$(eval $(call libbtsha1,build_variants/$(v),build_variants/$(v)/libbtsha1.so,$(SCHED_$(v)),,-sched-$(v),$(HOSTOBJ),$(SONAME))))
 
 # Microbenchmarks behind the measurements in profiles/ (not part of the product).
 UB_SRC := $(wildcard tools/ubench/*.hip)

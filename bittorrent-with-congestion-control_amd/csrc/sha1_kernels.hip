@@ -470,7 +470,7 @@ __device__ __forceinline__ void lat_rounds(State &st, const u32x4 (&q)[20]) {
 // CU and their waves share SIMDs (32768 chunks: 6.8 ms vs 11.3 ms).
 // MID: one COLUMN of each chunk -- len bytes (a 64-byte multiple) at `pitch`
 // from the previous chunk's column -- for the host pipeline's column-split
-// last batch (bt_sha1_api.cpp, chunks_host_on), each chunk's chaining state
+// last batch (bt_pipeline.cpp, HostFeed), each chunk's chaining state
 // carried between launches in `state` (word k of chunk i at state[k*n_chunks
 // + i]; SHA1Context.hash, sha.c:446-450):
 //   kLatWhole  (0): whole chunks: IV, blocks, MD padding, digest;
@@ -1139,7 +1139,7 @@ __global__ __launch_bounds__(kBlock) void k_lookup_query(const uint8_t *__restri
 }  // namespace btsha1
 
 // ---------------------------------------------------------------------------
-// Launchers (C++ linkage, used by the C-ABI layer in bt_sha1_api.cpp).
+// Launchers (C++ linkage, used by the host runtime, bt_*.cpp).
 // ---------------------------------------------------------------------------
 using namespace btsha1;
 

@@ -1,5 +1,5 @@
 // sha1_launch.h -- internal launcher interface between the kernels
-// (sha1_kernels.hip) and the C-ABI runtime (bt_sha1_api.cpp).
+// (sha1_kernels.hip) and the host runtime (bt_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -55,6 +55,73 @@ def test_variant_libraries_export_every_declared_symbol(variant):
     assert not names - exported, names - exported
 
 
+# What the library exports besides the functions include/*.h declare, taken
+# from `nm -D --defined-only` of the last build with the whole host runtime in
+# one translation unit (everything internal in an anonymous namespace there).
+NON_PUBLIC_EXPORTS = set("""
+_Z17btsha1_device_cusv
+_Z18btsha1_chain_batchv
+_Z18btsha1_launch_fillPvmmmP12ihipStream_t
+_Z19btsha1_launch_chainPKvPKmPKjmmmPhP12ihipStream_tmPKhS5_
+_Z19btsha1_launch_fixedPKvmjjPhPKhS1_P12ihipStream_tij
+_Z20btsha1_latency_batchv
+_Z20btsha1_launch_columnPKvmjjiPjmPhP12ihipStream_tPKhS2_
+_Z20btsha1_launch_lookupPKhmS0_mPjjPlP12ihipStream_t
+_Z20btsha1_launch_raggedPKvPKmPKjmjmPhP12ihipStream_t
+_Z22btsha1_set_chain_batchm
+_Z23btsha1_fixed_variant_oki
+_Z23btsha1_launch_chain_onePKvmPhP12ihipStream_tPjj
+_Z24btsha1_experiments_buildv
+_Z24btsha1_fixed_kernel_namemi
+_Z24btsha1_set_latency_batchm
+_Z26btsha1_chain_batch_settingv
+_Z26btsha1_debug_barrier_statsPmi
+_Z27btsha1_launch_fixed_stampedPKvmjjPhPmP12ihipStream_ti
+_Z28btsha1_latency_batch_settingv
+_Z28btsha1_launch_chain_midstatePjPKvmP12ihipStream_tS_j
+_ZN16bt_sha1_verifierD2Ev
+_ZNSt11_Deque_baseI15bt_sha1_verdictSaIS0_EE17_M_initialize_mapEm
+_ZNSt11_Deque_baseIjSaIjEE17_M_initialize_mapEm
+_ZNSt5dequeI15bt_sha1_verdictSaIS0_EE16_M_push_back_auxIJRKS0_EEEvDpOT_
+_ZNSt5dequeI15bt_sha1_verdictSaIS0_EE17_M_reallocate_mapEmb
+_ZNSt5dequeIjSaIjEE16_M_push_back_auxIJRKjEEEvDpOT_
+_ZNSt5dequeIjSaIjEE17_M_reallocate_mapEmb
+_ZNSt5dequeIjSaIjEED2Ev
+_ZNSt6vectorI6VBatchSaIS0_EE17_M_default_appendEm
+_ZNSt6vectorI6VBatchSaIS0_EED2Ev
+_ZNSt6vectorINSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEESaIS5_EEC2EmRKS6_
+_ZNSt6vectorINSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEESaIS5_EED2Ev
+_ZNSt6vectorIS_IiSaIiEESaIS1_EE17_M_default_appendEm
+_ZNSt6vectorISt6threadSaIS0_EED2Ev
+_ZNSt6vectorIhSaIhEE14_M_fill_assignEmRKh
+_ZNSt6vectorIlSaIlEEC2EmRKlRKS0_
+_ZNSt6vectorImSaImEE17_M_default_appendEm
+_ZNSt7__cxx119to_stringEi
+_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEOS8_PKS5_
+_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEOS8_RKS8_
+_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEOS8_S9_
+_ZStplIcSt11char_traitsIcESaIcEENSt7__cxx1112basic_stringIT_T0_T1_EEPKS5_OS8_
+""".split())
+# The two families whose names differ from build to build: the kernels'
+# handles and host stubs (sha1_kernels.hip; the experiments build has more of
+# them), and the per-file id the HIP compiler emits, a hash of the file's path.
+NON_PUBLIC_FAMILIES = re.compile(r"_ZN6btsha1\d+(__device_stub__)?k_[a-z]\w*|__hip_cuid_[0-9a-f]+")
+
+
+@pytest.mark.parametrize("lib", [LIB] + [os.path.join(REPO, "build_variants", v, "libbtsha1.so")
+                                         for v in ("dbgbar", "experiments")],
+                         ids=["product", "dbgbar", "experiments"])
+def test_library_exports_nothing_beyond_the_known_set(lib):
+    """The host runtime's internals are shared between its source files in a
+    namespace with hidden visibility: none of them, and no new template
+    instantiation, may show up among the dynamic symbols."""
+    assert os.path.exists(lib), "run make first"
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    extra = {s for s in exported - declared_functions() - NON_PUBLIC_EXPORTS if not NON_PUBLIC_FAMILIES.fullmatch(s)}
+    assert not extra, sorted(extra)
+
+
 def test_column_dev_refuses_null_buffers_before_any_device_call():
     """bt_sha1_column_dev: no chunks is no work, null buffers are -1 with a
     message -- both before a device is looked for, so they hold without one."""

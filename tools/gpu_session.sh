@@ -238,7 +238,7 @@ for step in "$@"; do
     latency) run latency 300 python3 tools/latency_bench.py ;;
     numa) run numa 600 python3 tools/numa_probe.py 4 ;;
     copy_order)
-      # A/B of the direct-DMA copy order (bt_sha1_api.cpp serial_copies), both legs forced
+      # A/B of the direct-DMA copy order (bt_pipeline.cpp serial_copies), both legs forced
       for rep in 1 2; do
         run "co_overlap_$rep" 600 env BT_SHA1_COPY_ORDER=overlap python3 tools/numa_probe.py 8 && \
         run "co_serial_$rep" 600 env BT_SHA1_COPY_ORDER=serial python3 tools/numa_probe.py 8 || exit 1
