@@ -14,8 +14,10 @@ The child process loads that build (BT_SHA1_LIB) and runs, each pinned to its
 kernel: tails with r >= 56 and r < 56, the chain kernel at 63/64/65 and
 128/129 blocks (its 64-block loader batches), the streaming API's midstate
 launches, the 2- and 3-slot forms of k_sha1_lat (1 and > 1 workgroups per CU)
-incl. the fused verify and an image tail, and ragged batches whose longest
-message sits in the LAST lane of its workgroup.  For every case it checks
+incl. the fused verify, an image tail and chunks of one or two blocks in all
+(0, 55, 56 and 64 bytes), and ragged batches whose longest message sits in the
+LAST lane of its workgroup or whose workgroups hold only messages of one or
+two blocks.  For every case it checks
 the digests against the oracle, zero misses, and the EXACT wave and barrier
 totals computed here from the invariant -- so the tallies prove the counting
 build is what ran, and which kernel (S/R pairs per workgroup) ran.
@@ -129,16 +131,45 @@ def _child():
     got = bt.chunks_host(img, 1024)
     want_dig = [orc.sha1(img[i:i + 1024]) for i in range(0, len(img), 1024)]
     record("lat image + tail r=60", (6, 2 * 2 * (nb_total(1024) + 1) + 2 * (nb_total(1020) + 1)), got == want_dig)
+    # one and two blocks in all (nb_total = 1, 1, 2, 2): at 3 slots R's loop takes its b + 1 / b + 2
+    # fallbacks on the first trip and S's closing barriers pair with R's opening ones
+    fixed("lat 3-slot len=0", 64 * cus + 1, 0, 16, "k_sha1_lat", 206)
+    fixed("lat 3-slot len=55", 64 * cus + 1, 55, 64, "k_sha1_lat", 207)
+    fixed("lat 3-slot len=56", 64 * cus + 1, 56, 64, "k_sha1_lat", 208)
+    fixed("lat 3-slot len=64", 64 * cus + 1, 64, 64, "k_sha1_lat", 209)
+    fixed("lat 2-slot len=0", 100, 0, 16, "k_sha1_lat", 210)
 
-    # ---- k_sha1_lat_ragged: the wave runs to its longest message; put it in lane 63
+    # ---- k_sha1_lat_ragged: the wave runs to its longest message
     pin(chain=False, lat=True)
-    for name, n, seed in (("lat_ragged 2-slot", 600, 300), ("lat_ragged 3-slot", 64 * cus + 100, 301)):
-        import random
-        rng = random.Random(seed)
+    import random
+
+    def longest_in_lane_63(rng, n):
         lens = [rng.randrange(0, 1500) for _ in range(n)]
         for g in range(0, n, 64):
             last = min(g + 63, n - 1)
             lens[last] = 1600 + 60 if (g // 64) % 2 else 1600 + 20  # longest, r >= 56 on every other group
+        return lens
+
+    def short_workgroups(rng, n):
+        """Workgroups of messages under 56 bytes (nbmax == 1) alternating with
+        workgroups under 120 bytes that hold one of 56 or more (nbmax == 2)."""
+        lens = []
+        for g in range(0, n, 64):
+            m = min(64, n - g)
+            if (g // 64) % 2:
+                part = [rng.randrange(0, 120) for _ in range(m)]
+                part[rng.randrange(m)] = rng.randrange(56, 120)
+            else:
+                part = [rng.randrange(0, 56) for _ in range(m)]
+            lens += part
+        return lens
+
+    for name, n, seed, recipe in (("lat_ragged 2-slot", 600, 300, longest_in_lane_63),
+                                  ("lat_ragged 3-slot", 64 * cus + 100, 301, longest_in_lane_63),
+                                  ("lat_ragged 3-slot nbmax 1 and 2", 64 * cus + 100, 302, short_workgroups),
+                                  ("lat_ragged 2-slot nbmax 1 and 2", 600, 303, short_workgroups)):
+        rng = random.Random(seed)
+        lens = recipe(rng, n)
         blob, offs = bytearray(), []
         for i, ln in enumerate(lens):
             blob += bytes(i % 5)  # odd alignments
@@ -171,7 +202,7 @@ def test_barrier_accounting_build_matches_invariant():
     line = [l for l in r.stdout.splitlines() if l.startswith("BARRIER_RESULTS ")]
     assert len(line) == 1, r.stdout[-2000:]
     results = json.loads(line[0].split(" ", 1)[1])
-    assert len(results) == 27
+    assert len(results) == 34
     bad = [c for c in results if not c["digests_ok"] or c["got"][2] != 0 or c["got"][:2] != c["want"]]
     assert not bad, bad
 

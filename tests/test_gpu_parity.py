@@ -1403,8 +1403,12 @@ def test_ragged_latency_kernel_mixed_lengths(bt, torch, oracle, n):
     """k_sha1_lat_ragged: 64 messages per workgroup with unequal lengths (so
     lanes finish at different blocks and latch their own state), every
     residue mod 64 incl. messages shorter than one block (those lanes read a
-    static zero block), odd offsets; and the launch past one workgroup per CU
-    (three-slot form) at n = 4099.  Against the oracle."""
+    static zero block), odd offsets; 2, 10 and 65 workgroups.  Against the
+    oracle.  All three stay at or under one workgroup per CU on a full MI355X
+    (256 CUs), so they run the two-slot form; the three-slot form (more than
+    `cus` workgroups) is tested in test_gpu_launch_forms.py
+    (test_launch_forms_lat_ragged_short_workgroups) and, with its barrier
+    counts, in test_gpu_barriers.py."""
     rng = random.Random(n)
     lens = [rng.choice([0, 1, 55, 56, 63, 64, 65, 119, 120, 1000, rng.randrange(0, 40000)]) for _ in range(n)]
     offs, pos = [], 0
