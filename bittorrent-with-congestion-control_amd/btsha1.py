@@ -100,6 +100,25 @@ _sig("bt_sha1_verifier_poll", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes
 _sig("bt_sha1_verifier_drain", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
 _sig("bt_sha1_verifier_pending", _i64, _vp)
 _sig("bt_sha1_lookup_dev", ctypes.c_int, _vp, _u64, _vp, _u64, _vp, _vp)
+_sig("bt_sha1_states_init_dev", ctypes.c_int, _vp, _u64, _vp)
+_sig("bt_sha1_resume_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
+
+
+class ReceiverStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_receiver_stats
+    _fields_ = [("launches", ctypes.c_uint64), ("advance_launches", ctypes.c_uint64),
+                ("advanced_bytes", ctypes.c_uint64), ("committed", ctypes.c_uint64), ("released", ctypes.c_uint64)]
+
+
+_sig("bt_sha1_receiver_create", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+_sig("bt_sha1_receiver_destroy", None, _vp)
+_sig("bt_sha1_receiver_slot", _vp, _vp)
+_sig("bt_sha1_receiver_advance", ctypes.c_int, _vp, _vp, ctypes.c_uint32)
+_sig("bt_sha1_receiver_commit", ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp, _u64)
+_sig("bt_sha1_receiver_release", ctypes.c_int, _vp, _vp)
+_sig("bt_sha1_receiver_poll", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
+_sig("bt_sha1_receiver_drain", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
+_sig("bt_sha1_receiver_pending", _i64, _vp)
+_sig("bt_sha1_receiver_get_stats", ctypes.c_int, _vp, ctypes.POINTER(ReceiverStats))
 
 
 class ChunkEntry(ctypes.Structure):
@@ -220,6 +239,22 @@ def column_dev(d_col, n, pitch, width, part, d_state, msg_len=0, d_digests=None,
 
 def ragged_dev(d_base, d_offsets, d_lens, n, d_digests, stream=None):
     _check(lib.bt_sha1_ragged_dev(d_base, d_offsets, d_lens, n, d_digests, stream), "bt_sha1_ragged_dev")
+
+
+def states_init_dev(d_states, n, stream=None):
+    """d_states[5*i ..] = the SHA-1 IV for i < n: where resume_dev starts."""
+    _check(lib.bt_sha1_states_init_dev(d_states, n, stream), "bt_sha1_states_init_dev")
+
+
+def resume_dev(d_base, d_offsets, d_lens, d_totals, n, d_states, d_digests=None, d_expected=None, d_ok=None,
+               stream=None):
+    """One launch of the resumable chain kernel over n messages that are still
+    arriving: message i's next d_lens[i] (uint32) bytes at d_base +
+    d_offsets[i] (uint64), its chaining state at d_states[5*i ..].
+    d_totals[i] (uint64) == 0 advances the state over the whole blocks;
+    != 0 finishes a message of that many bytes into d_digests / d_ok."""
+    _check(lib.bt_sha1_resume_dev(d_base, d_offsets, d_lens, d_totals, n, d_states, d_digests, d_expected, d_ok,
+                                  stream), "bt_sha1_resume_dev")
 
 
 def fill_synthetic(d_buf, nbytes, first_word, seed, stream=None):
@@ -478,6 +513,85 @@ class Verifier:
     def close(self):
         if self.h:
             lib.bt_sha1_verifier_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+NEVER = 0xFFFFFFFF  # Receiver stride: nothing is hashed before commit
+
+
+class Receiver:
+    """Progressive receive (bt_sha1_receiver_*): a chunk is hashed while its
+    payloads arrive, so commit leaves only the last stride and the padding."""
+
+    def __init__(self, device=0, chunk_len=CHUNK, nslots=4, stride=0):
+        self.h = lib.bt_sha1_receiver_create(device, chunk_len, nslots, stride)
+        if not self.h:
+            raise BtSha1Error(f"bt_sha1_receiver_create: {last_error()}")
+        self.chunk_len = chunk_len
+
+    def slot(self):
+        """Hand out a pinned slot (integer address) to receive a chunk into, in order."""
+        p = lib.bt_sha1_receiver_slot(self.h)
+        if not p:
+            raise BtSha1Error(f"bt_sha1_receiver_slot: {last_error()}")
+        return p
+
+    def advance(self, slot, filled):
+        """Bytes [0, filled) of the slot are final."""
+        _check(lib.bt_sha1_receiver_advance(self.h, slot, filled), "bt_sha1_receiver_advance")
+
+    def commit(self, slot, expected, tag, length=None):
+        e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
+        _check(lib.bt_sha1_receiver_commit(self.h, slot, self.chunk_len if length is None else length, e, tag),
+               "bt_sha1_receiver_commit")
+
+    def release(self, slot):
+        _check(lib.bt_sha1_receiver_release(self.h, slot), "bt_sha1_receiver_release")
+
+    def receive(self, chunk, expected, tag, piece=1484):
+        """A whole chunk as the peer's receive path delivers it: `piece`-byte
+        payloads appended in order (util.c:275), advance after each, commit."""
+        p = self.slot()
+        data = bytes(chunk)
+        for o in range(0, len(data), piece):
+            part = data[o:o + piece]
+            ctypes.memmove(p + o, part, len(part))
+            self.advance(p, o + len(part))
+        self.commit(p, expected, tag, len(data))
+
+    def _collect(self, fn, max_n=256):
+        out = (Verdict * max_n)()
+        got = _check(fn(self.h, out, max_n), "receiver")
+        return [(out[i].tag, bool(out[i].ok), bytes(out[i].digest)) for i in range(got)]
+
+    def poll(self):
+        return self._collect(lib.bt_sha1_receiver_poll)
+
+    def drain(self):
+        res = []
+        while True:
+            r = self._collect(lib.bt_sha1_receiver_drain)
+            if not r:
+                return res
+            res += r
+
+    def pending(self):
+        return lib.bt_sha1_receiver_pending(self.h)
+
+    def stats(self):
+        s = ReceiverStats()
+        _check(lib.bt_sha1_receiver_get_stats(self.h, ctypes.byref(s)), "bt_sha1_receiver_get_stats")
+        return {k: int(getattr(s, k)) for k, _ in ReceiverStats._fields_}
+
+    def close(self):
+        if self.h:
+            lib.bt_sha1_receiver_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -799,6 +799,132 @@ __global__ __launch_bounds__(128) void k_sha1_chain(const uint8_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Resumable chain kernel: the chain kernel's S / R split over a message that
+// is still arriving (the peer's receive path, util.c:250-337: payloads are
+// appended in order, util.c:275, and only the complete chunk is hashed,
+// util.c:311-313).  SHA-1 resumes at every 64-byte boundary, so each launch
+// takes a chaining state in SHA1Context.hash order and either ADVANCES it
+// over the whole blocks that have arrived or FINISHES the message from it.
+// blockIdx.x = message i, one two-wave workgroup each:
+//   bytes   base + offsets[i], lens[i] of them, any alignment; a launch reads
+//           no byte at or past offsets[i] + lens[i] (the caller may be writing
+//           there): whole blocks and the r tail bytes only, as chain_block does
+//   state   states[5*i .. 5*i+4], device or pinned host memory
+//   totals[i] == 0  advance: the lens[i] >> 6 whole blocks are compressed and
+//           lane 0 stores the state back (lens[i] == 0 leaves it as it was);
+//           nothing else is written
+//   totals[i] != 0  finish: lens[i] are the last bytes of a totals[i]-byte
+//           message whose first totals[i] - lens[i] bytes (a 64-byte multiple)
+//           were advanced before; S lays out the tail, the 0x80 mark and the
+//           length totals[i] * 8 (sha.c:536-543), lane 0 writes digest i
+//           (big-endian, any alignment; digests may be NULL) and, with VERIFY,
+//           ok[i] = digest i == expected[20*i ..] (util.c:313).  The state is
+//           not written back.
+// offsets == NULL is the single-message form (grid 1): offset, length and
+// total ride in the kernel arguments off1 / len1 / total1.
+// Barrier accounting as in k_sha1_chain: both waves execute nbatch + 1, with
+// nbatch = ceil(nb / 64) and nb = lens >> 6 for an advance, (lens >> 6) +
+// (r >= 56 ? 2 : 1) for a finish.
+// ---------------------------------------------------------------------------
+template <bool VERIFY>
+__global__ __launch_bounds__(128) void k_sha1_resume(const uint8_t *__restrict__ base,
+                                                     const uint64_t *__restrict__ offsets,
+                                                     const uint32_t *__restrict__ lens,
+                                                     const uint64_t *__restrict__ totals, uint64_t off1, uint32_t len1,
+                                                     uint64_t total1, uint32_t *__restrict__ states,
+                                                     uint8_t *__restrict__ digests, const uint8_t *__restrict__ expected,
+                                                     uint8_t *__restrict__ ok, uint32_t *__restrict__ done,
+                                                     uint32_t seq) {
+  __shared__ u32x4 lds[2][kChainStride * kChainBatch];  // as k_sha1_chain: 2 slots x 64 blocks, 42 KiB
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t i = blockIdx.x;
+  const uint8_t *p = base + (offsets ? offsets[i] : off1);
+  const uint32_t len = offsets ? lens[i] : len1;
+  const uint64_t total = offsets ? totals[i] : total1;
+  const bool fin = total != 0;  // workgroup-uniform: both waves agree
+  const uint64_t nfull = len >> 6;
+  const uint32_t r = len & 63u;
+  const uint64_t nb_total = fin ? nfull + (r >= 56u ? 2u : 1u) : nfull;
+  const uint64_t nbatch = (nb_total + kChainBatch - 1) / kChainBatch;
+  uint32_t *st_io = states + 5 * i;
+  uint32_t nbar = 0;
+  (void)nbar;
+  if (wave == 0) {
+    // ---- S: lane j prepares block b0 + j ----------------------------------
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const uint64_t g = bt * kChainBatch + lane;
+      const uint64_t gc = g < nb_total ? g : nb_total;  // lanes past the end: a block that reads nothing
+      uint32_t w[16];
+      if (fin) chain_block<false>(w, p, gc, nfull, r, total * 8ull);
+      else chain_block<true>(w, p, gc, nfull, 0u, 0ull);
+      produce_wk<0, 80, 1, kChainStride>(w, lds[bt & 1u], lane);
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_BARRIER(nbar);  // pairs with R's last barrier
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+  } else {
+    // ---- R: the chain, from the state the last launch left ------------------
+    State st;
+    st.h0 = st_io[0]; st.h1 = st_io[1]; st.h2 = st_io[2]; st.h3 = st_io[3]; st.h4 = st_io[4];
+    BT_LAT_BARRIER(nbar);  // batch 0 is in slot 0
+    const uint32_t l16 = lane & 15u, l4 = lane & 3u;
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const u32x4 *slot = lds[bt & 1u];
+      const uint64_t left = nb_total - bt * kChainBatch;
+      const uint32_t nb = left < kChainBatch ? (uint32_t)left : kChainBatch;
+      // Block k+1's two reads are issued before block k's rounds.
+      u32x4 A = slot[l16], B = slot[16 + l4];
+      for (uint32_t k = 0; k < nb; ++k) {
+        const u32x4 *nxt = slot + (k + 1 < nb ? k + 1 : k) * kChainStride;
+        const u32x4 An = nxt[l16], Bn = nxt[16 + l4];
+        chain_rounds(st, A, B);
+        A = An;
+        B = Bn;
+      }
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+    if (lane == 0) {
+      if (!fin) {
+        st_io[0] = st.h0; st_io[1] = st.h1; st_io[2] = st.h2; st_io[3] = st.h3; st_io[4] = st.h4;
+      } else {
+        const uint32_t h[5] = {st.h0, st.h1, st.h2, st.h3, st.h4};
+        if (digests) {
+          uint8_t *o = digests + 20 * i;
+#pragma unroll
+          for (int k = 0; k < 5; ++k) {  // sha.c:550-553
+            o[4 * k] = (uint8_t)(h[k] >> 24);
+            o[4 * k + 1] = (uint8_t)(h[k] >> 16);
+            o[4 * k + 2] = (uint8_t)(h[k] >> 8);
+            o[4 * k + 3] = (uint8_t)h[k];
+          }
+        }
+        if constexpr (VERIFY) {  // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+          const uint8_t *x = expected + 20 * i;
+          uint32_t diff = 0;
+#pragma unroll
+          for (int k = 0; k < 20; ++k) diff |= (uint32_t)x[k] ^ ((h[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu);
+          ok[i] = diff == 0;
+        }
+      }
+      // Completion word, as k_sha1_chain's: released at system scope after the results.
+      if (done) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// d_states[5*i ..] = the SHA-1 IV (sha.c:149-163): where k_sha1_resume starts.
+__global__ __launch_bounds__(kBlock) void k_states_init(uint32_t *__restrict__ states, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  State st;
+  st.init();
+  uint32_t *o = states + 5 * i;
+  o[0] = st.h0; o[1] = st.h1; o[2] = st.h2; o[3] = st.h3; o[4] = st.h4;
+}
+
+// ---------------------------------------------------------------------------
 // Latency kernel for RAGGED batches (bt_sha1_ragged_dev with 2 x CUs < n <=
 // 128 x CUs messages): k_sha1_lat's loader / round-wave split with per-lane
 // message pointers and lengths.  Lane j of both waves owns message 64*wg + j;
@@ -1415,6 +1541,44 @@ hipError_t btsha1_launch_chain(const void *base, const uint64_t *offsets, const 
   else
     hipLaunchKernelGGL((k_sha1_chain<false, false>), dim3((uint32_t)grid), dim3(128), 0, s, (const uint8_t *)base,
                        offsets, lens, pitch, fixed_len, tail_len, nullptr, digests, expected, ok, nullptr, 0u);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_resume(const void *base, const uint64_t *offsets, const uint32_t *lens, const uint64_t *totals,
+                                uint64_t n, uint32_t *states, uint8_t *digests, const uint8_t *expected, uint8_t *ok,
+                                hipStream_t s, uint32_t *done, uint32_t seq) {
+  if (n == 0) return hipSuccess;
+  if (n > BTSHA1_RESUME_MAX || !base || !offsets || !lens || !totals || !states || (ok && !expected) ||
+      (done && n != 1))
+    return hipErrorInvalidValue;
+  if (ok)
+    hipLaunchKernelGGL(k_sha1_resume<true>, dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)base, offsets, lens,
+                       totals, 0ull, 0u, 0ull, states, digests, expected, ok, done, seq);
+  else
+    hipLaunchKernelGGL(k_sha1_resume<false>, dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)base, offsets, lens,
+                       totals, 0ull, 0u, 0ull, states, digests, expected, ok, done, seq);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state, uint8_t *digest,
+                                    const uint8_t *expected, uint8_t *ok, hipStream_t s, uint32_t *done,
+                                    uint32_t seq) {
+  if (!data || !state || (ok && !expected) || (total && total < len) || (total && ((total - len) & 63u)))
+    return hipErrorInvalidValue;
+  if (ok)
+    hipLaunchKernelGGL(k_sha1_resume<true>, dim3(1), dim3(128), 0, s, (const uint8_t *)data, nullptr, nullptr, nullptr,
+                       0ull, len, total, state, digest, expected, ok, done, seq);
+  else
+    hipLaunchKernelGGL(k_sha1_resume<false>, dim3(1), dim3(128), 0, s, (const uint8_t *)data, nullptr, nullptr, nullptr,
+                       0ull, len, total, state, digest, expected, ok, done, seq);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_states_init(uint32_t *d_states, uint64_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint64_t grid = (n + kBlock - 1) / kBlock;
+  if (!d_states || grid > BTSHA1_RESUME_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_states_init, dim3((uint32_t)grid), dim3(kBlock), 0, s, d_states, n);
   return hipGetLastError();
 }
 

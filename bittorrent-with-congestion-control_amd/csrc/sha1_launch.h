@@ -63,6 +63,32 @@ hipError_t btsha1_launch_chain_one(const void *msg, uint64_t len, uint8_t *diges
 hipError_t btsha1_launch_chain(const void *base, const uint64_t *offsets, const uint32_t *lens, uint64_t pitch,
                                uint64_t fixed_len, uint64_t n, uint8_t *digests, hipStream_t s, uint64_t tail_len = 0,
                                const uint8_t *expected = nullptr, uint8_t *ok = nullptr);
+// Resumable chain kernel (k_sha1_resume; one two-wave workgroup per message):
+// message i's next lens[i] bytes at base + offsets[i] (any alignment, device or
+// pinned host memory; nothing at or past offsets[i] + lens[i] is read), its
+// chaining state at states[5*i ..] (SHA1Context.hash order, device or pinned
+// host memory).  totals[i] == 0 advances the state over the lens[i] >> 6 whole
+// blocks; totals[i] != 0 finishes a totals[i]-byte message whose first
+// totals[i] - lens[i] bytes (a 64-byte multiple) were advanced before: digest
+// i (big-endian, any alignment) to digests + 20*i when digests != NULL, and
+// with ok (needs expected) ok[i] = digest i == expected[20*i ..]; entries of
+// advancing messages are left alone.  done != NULL (n == 1 only): the
+// completion word of btsha1_launch_chain_midstate.  At most BTSHA1_RESUME_MAX
+// messages per launch (the grid).  New launchers are hidden: shared between
+// the library's objects, absent from its dynamic symbols.
+#define BTSHA1_RESUME_MAX 0x7fffffffull
+#define BTSHA1_HIDDEN __attribute__((visibility("hidden")))
+BTSHA1_HIDDEN hipError_t btsha1_launch_resume(const void *base, const uint64_t *offsets, const uint32_t *lens,
+                                              const uint64_t *totals, uint64_t n, uint32_t *states, uint8_t *digests,
+                                              const uint8_t *expected, uint8_t *ok, hipStream_t s,
+                                              uint32_t *done = nullptr, uint32_t seq = 0);
+// The single-message form (grid 1): offset, length and total are kernel
+// arguments, so a host object launches it with no device-side arrays.
+BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,
+                                                  uint8_t *digest, const uint8_t *expected, uint8_t *ok, hipStream_t s,
+                                                  uint32_t *done = nullptr, uint32_t seq = 0);
+// d_states[5*i ..] = the SHA-1 IV (sha.c:149-163) for i < n.
+BTSHA1_HIDDEN hipError_t btsha1_launch_states_init(uint32_t *d_states, uint64_t n, hipStream_t s);
 // One column of n equal chunks (k_sha1_lat's column forms): chunk i's column
 // is `width` bytes (a 64-byte multiple) at d_col + i*pitch; d_state holds
 // each chunk's chaining state between columns (5 x n words, word k of chunk i

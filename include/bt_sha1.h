@@ -147,6 +147,35 @@ int bt_sha1_verify_dev(const void *d_in, uint64_t n, uint64_t chunk_len, uint64_
 /* n messages, message i = d_base[d_offsets[i] .. + d_lens[i]). */
 int bt_sha1_ragged_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
                        uint64_t n, uint8_t *d_digests, void *stream);
+/* Resumable hashing of messages that are still arriving (a peer appends a
+ * chunk's payloads in order, util.c:275, and hashes it only when complete,
+ * util.c:311-313; SHA-1 resumes at every 64-byte boundary).  This is the
+ * LATENCY form: one two-wave workgroup per message, any n, meant for the
+ * handful of chunks a peer has in flight -- batches of whole chunks belong to
+ * bt_sha1_chunks_dev.
+ * bt_sha1_states_init_dev: d_states[5*i ..] = the SHA-1 IV (sha.c:149-163)
+ * for i < n.
+ * bt_sha1_resume_dev: n messages, one launch.  Message i's next d_lens[i]
+ * bytes are at d_base + d_offsets[i] (any alignment; device or pinned host
+ * memory; no byte at or past d_offsets[i] + d_lens[i] is read, so the caller
+ * may be writing there), its chaining state at d_states[5*i ..] in
+ * SHA1Context.hash order (device or pinned host memory).
+ *   d_totals[i] == 0: advance -- the d_lens[i] / 64 whole blocks are
+ *     compressed into the state; d_lens[i] == 0 leaves it as it was.
+ *   d_totals[i] != 0: finish -- d_lens[i] are the last bytes (any count, 0
+ *     included) of a d_totals[i]-byte message whose first d_totals[i] -
+ *     d_lens[i] bytes, a 64-byte multiple, were advanced before; the padding
+ *     of sha.c:536-543 is appended and digest i written.  The state is not
+ *     written back.
+ * d_digests / d_expected / d_ok as in bt_sha1_verify_dev (d_digests may be
+ * NULL, and any alignment is taken): d_ok needs d_expected; entries of
+ * advancing messages are left untouched.  n == 0 is no work; null d_base /
+ * d_offsets / d_lens / d_totals / d_states, d_ok without d_expected, or n
+ * above 2^31 - 1 (the grid) are -1 before any device call. */
+int bt_sha1_states_init_dev(uint32_t *d_states, uint64_t n, void *stream);
+int bt_sha1_resume_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+                       const uint64_t *d_totals, uint64_t n, uint32_t *d_states, uint8_t *d_digests,
+                       const uint8_t *d_expected, uint8_t *d_ok, void *stream);
 /* Frozen generator: 64-bit word g of the stream = splitmix64(seed + g), LE.
  * Writes words first_word .. into d_buf (16-byte aligned), nbytes bytes. */
 int bt_sha1_fill_synthetic(void *d_buf, uint64_t nbytes, uint64_t first_word, uint64_t seed,
@@ -294,6 +323,58 @@ int bt_sha1_verifier_poll(bt_sha1_verifier *v, bt_sha1_verdict *out, int max);
 int bt_sha1_verifier_drain(bt_sha1_verifier *v, bt_sha1_verdict *out, int max);
 /* Verdicts not yet returned (in flight + finished-unpolled). */
 int64_t bt_sha1_verifier_pending(bt_sha1_verifier *v);
+
+/* ---- progressive receive (util.c:250-337 for in-order delivery) ---------- */
+/* The verifier above starts a chunk's serial chain when its last byte has
+ * arrived (~6 ms per 512 KiB).  The receiver hashes a chunk WHILE it is
+ * received: the GPU advances each in-progress chunk's chaining state over the
+ * prefix that has arrived (the resumable chain kernel reads the pinned slot
+ * in place over PCIe, no H2D copy), so commit leaves only the last stride and
+ * the padding.  One thread per object, like the verifier.
+ * nslots: chunks in flight (the peer's max_conn), 1..64; chunk_len: 1 .. 32
+ * MiB; stride: bytes of new whole blocks that trigger a launch (0 = 64 KiB;
+ * UINT32_MAX = never before commit).  NULL with a message for arguments out
+ * of range, before any device call. */
+typedef struct bt_sha1_receiver bt_sha1_receiver;
+bt_sha1_receiver *bt_sha1_receiver_create(int device, uint32_t chunk_len, uint32_t nslots,
+                                          uint32_t stride);
+void bt_sha1_receiver_destroy(bt_sha1_receiver *r);
+/* A pinned chunk_len-byte slot to receive one chunk into, in order
+ * (save_data_packet's memcpy target, util.c:275); its chaining state starts
+ * from the IV.  NULL with a message when all nslots are out. */
+uint8_t *bt_sha1_receiver_slot(bt_sha1_receiver *r);
+/* Bytes [0, filled) of the slot are final (received_byte_number): `filled`
+ * never decreases and is at most chunk_len.  Once the whole blocks not yet
+ * hashed reach `stride` bytes, ONE launch over them is queued; returns
+ * without waiting. */
+int bt_sha1_receiver_advance(bt_sha1_receiver *r, uint8_t *slot, uint32_t filled);
+/* The chunk is complete at len bytes (hashed so far <= len <= chunk_len,
+ * len > 0; a short last chunk is fine): queues the finishing launch over the
+ * rest with the compare against expected[20] fused, and returns without
+ * waiting.  The verdict arrives through poll / drain; the slot is free again
+ * once its verdict has been returned. */
+int bt_sha1_receiver_commit(bt_sha1_receiver *r, uint8_t *slot, uint32_t len,
+                            const uint8_t expected[20], uint64_t tag);
+/* Give an outstanding slot back (aborted download): waits for its queued
+ * launches; no verdict.  The slot restarts from the IV when handed out again. */
+int bt_sha1_receiver_release(bt_sha1_receiver *r, uint8_t *slot);
+/* Non-blocking: reads the kernels' completion words (no stream wait) and
+ * copies up to max finished verdicts out, in the order they were found
+ * finished; returns the count. */
+int bt_sha1_receiver_poll(bt_sha1_receiver *r, bt_sha1_verdict *out, int max);
+/* Blocking: waits for everything committed, returns up to max verdicts; -1 if
+ * a launch failed. */
+int bt_sha1_receiver_drain(bt_sha1_receiver *r, bt_sha1_verdict *out, int max);
+/* Verdicts not yet returned (in flight + finished-unpolled). */
+int64_t bt_sha1_receiver_pending(bt_sha1_receiver *r);
+typedef struct {
+  uint64_t launches;          /* kernel launches queued (advances + commits)  */
+  uint64_t advance_launches;  /* of them, queued by advance                   */
+  uint64_t advanced_bytes;    /* bytes hashed before their chunk's commit     */
+  uint64_t committed;         /* chunks committed                             */
+  uint64_t released;          /* slots released                               */
+} bt_sha1_receiver_stats;
+int bt_sha1_receiver_get_stats(bt_sha1_receiver *r, bt_sha1_receiver_stats *out);
 
 /* ---- digest lookup (get_chunk_id / find_chunk, util.c:3-39, on the GPU) - */
 /* d_index[q] = smallest i with digest d_table[i] == d_queries[q], else -1.

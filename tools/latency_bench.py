@@ -19,6 +19,21 @@ one JSON line per measurement (median of --reps):
   batch_<n>_<mode>  n device-resident 512 KiB chunks through the hot kernel
                     (fixed) or the two-wave latency kernel (lat), kernel time
   verifier_b1       bt_sha1_verifier with batch 1: submit -> verdict
+  receiver_commit_<stride>   bt_sha1_receiver: one 512 KiB chunk delivered in
+                    1484-byte payloads with advance after each, every earlier
+                    launch finished before the commit (as at network speed):
+                    commit -> verdict.  Strides: default (64 KiB), 4096 and
+                    never (UINT32_MAX: the whole chain at commit)
+  receiver_first_byte_<stride>  the same delivery fed back to back with no
+                    waiting: first byte -> verdict (what the extra launches
+                    cost when the data is already there)
+  resume_1x512k_<where>  one finishing launch of bt_sha1_resume_dev over a whole
+                    512 KiB message from the IV, kernel time: the message in
+                    device memory (dev) or read in place from pinned host
+                    memory (pinned), beside shahash_512k (k_sha1_chain on
+                    pinned host memory) in the same process
+--only receiver runs just the receiver rows, verifier_b1 and the resume rows
+(one process, so the rows compare on one box).
 Digests are checked against the oracle (hashlib is not used).
 """
 import argparse
@@ -47,6 +62,7 @@ def emit(name, samples_s, extra=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--only", choices=["all", "receiver"], default="all")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -56,6 +72,13 @@ def main():
     rng = np.random.default_rng(7)
     msg = bytes(orc.fill_synthetic(CHUNK, 0, orc.SEED_SYNTH))
     want = orc.sha1(msg)
+    if args.only == "receiver":
+        assert torch.cuda.is_available()
+        torch.zeros(1, device="cuda")  # torch's runtime first
+        receiver_rows(bt, torch, msg, want, max(args.reps, 50))
+        verifier_row(bt, msg, want, max(args.reps, 50))
+        resume_rows(bt, torch, msg, want, max(args.reps, 50))
+        return
 
     # shahash: host buffer in, 20 bytes out, synchronous (chunk.c:33-49).
     assert bt.shahash(msg) == want
@@ -200,16 +223,107 @@ def main():
     bt.set_chain_batch(prev_chain)
     del big
 
+    verifier_row(bt, msg, want, args.reps)
+    receiver_rows(bt, torch, msg, want, max(args.reps, 50))
+
+
+def verifier_row(bt, msg, want, reps):
     v = bt.Verifier(batch=1, nstreams=2)
     ts = []
-    for i in range(args.reps):
+    for i in range(reps + 1):
         t0 = time.perf_counter()
         v.submit(msg, want, tag=i)
         r = v.drain()
         ts.append(time.perf_counter() - t0)
         assert r == [(i, True, want)], r
     v.close()
-    emit("verifier_b1", ts)
+    emit("verifier_b1", ts[1:])
+
+
+def resume_rows(bt, torch, msg, want, reps):
+    host = torch.frombuffer(bytearray(msg), dtype=torch.uint8)
+    o = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ln = torch.full((1,), CHUNK, dtype=torch.int32, device="cuda")
+    tt = torch.full((1,), CHUNK, dtype=torch.int64, device="cuda")
+    st = torch.zeros(5, dtype=torch.int32, device="cuda")
+    dig = torch.zeros(20, dtype=torch.uint8, device="cuda")
+    bt.states_init_dev(st.data_ptr(), 1)
+    for where, buf in (("dev", host.cuda()), ("pinned", host.pin_memory())):
+        ts = []
+        for _ in range(reps + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            bt.resume_dev(buf.data_ptr(), o.data_ptr(), ln.data_ptr(), tt.data_ptr(), 1, st.data_ptr(), dig.data_ptr())
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b) * 1e-3)
+        assert dig.cpu().numpy().tobytes() == want, where
+        emit(f"resume_1x512k_{where}", ts[1:], {"kernel": "k_sha1_resume"})
+    ts = []
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        got = bt.shahash(msg)
+        ts.append(time.perf_counter() - t0)
+    assert got == want
+    emit("shahash_512k", ts[1:], {"kernel": "k_sha1_chain"})
+
+
+def receiver_rows(bt, torch, msg, want, reps):
+    """The progressive receiver on one 512 KiB chunk in 1484-byte payloads
+    (util.c:275), advance after each.  commit -> verdict with every earlier
+    launch finished first (a device synchronise stands for the network's
+    pace), then first byte -> verdict with the payloads fed back to back."""
+    import ctypes
+    src = (ctypes.c_uint8 * CHUNK).from_buffer_copy(msg)
+    addr = ctypes.addressof(src)
+    piece = 1484
+
+    def deliver(rx, p):
+        for o in range(0, CHUNK, piece):
+            n = min(piece, CHUNK - o)
+            ctypes.memmove(p + o, addr + o, n)
+            rx.advance(p, o + n)
+
+    def verdict(rx, tag):
+        while True:
+            r = rx.poll()
+            if r:
+                assert r == [(tag, True, want)], r
+                return
+
+    for name, stride in (("default", 0), ("4096", 4096), ("never", bt.NEVER)):
+        rx = bt.Receiver(nslots=2, stride=stride)
+        commit_ts, first_ts = [], []
+        for i in range(reps + 1):  # the first repetition warms the kernel and the streams up
+            p = rx.slot()
+            deliver(rx, p)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rx.commit(p, want, i)
+            verdict(rx, i)
+            commit_ts.append(time.perf_counter() - t0)
+        base = rx.stats()
+        for i in range(reps + 1):
+            p = rx.slot()
+            t0 = time.perf_counter()
+            deliver(rx, p)
+            rx.commit(p, want, i)
+            verdict(rx, i)
+            first_ts.append(time.perf_counter() - t0)
+        # the host's share of first byte -> verdict: the same payload copies and advance calls, nothing committed
+        host_ts = []
+        for i in range(5):
+            p = rx.slot()
+            t0 = time.perf_counter()
+            deliver(rx, p)
+            host_ts.append(time.perf_counter() - t0)
+            rx.release(p)
+        per_chunk = {"launches_per_chunk": base["launches"] // (reps + 1),
+                     "advanced_bytes_per_chunk": base["advanced_bytes"] // (reps + 1)}
+        rx.close()
+        emit(f"receiver_commit_{name}", commit_ts[1:], per_chunk)
+        emit(f"receiver_first_byte_{name}", first_ts[1:],
+             dict(per_chunk, host_feed_ms=round(statistics.median(host_ts) * 1e3, 4)))
 
 
 if __name__ == "__main__":
