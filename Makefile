@@ -29,7 +29,7 @@ lib: $(LIB)
 # The host runtime: bt_runtime carries the source id and is compiled for every
 # build of the library; the others do not depend on the build, so every
 # variant but asan (which instruments all host code) links the product's.
-HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_receiver bt_chunks
+HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_receiver bt_intake bt_chunks
 HOSTOBJ  := $(HOST:%=$(PKG)/build/%.o)
 KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h
 HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/sha.h include/chunk.h

@@ -121,6 +121,25 @@ _sig("bt_sha1_receiver_pending", _i64, _vp)
 _sig("bt_sha1_receiver_get_stats", ctypes.c_int, _vp, ctypes.POINTER(ReceiverStats))
 
 
+class IntakeStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_intake_stats
+    _fields_ = [(f, ctypes.c_uint64) for f in ("kicks", "launches", "entries", "max_entries", "advanced_bytes",
+                                               "committed", "released", "deferred")]
+
+
+_sig("bt_sha1_intake_create", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+_sig("bt_sha1_intake_destroy", None, _vp)
+_sig("bt_sha1_intake_slot", _vp, _vp)
+_sig("bt_sha1_intake_advance", ctypes.c_int, _vp, _vp, ctypes.c_uint32)
+_sig("bt_sha1_intake_commit", ctypes.c_int, _vp, _vp, ctypes.c_uint32, _vp, _u64)
+_sig("bt_sha1_intake_release", ctypes.c_int, _vp, _vp)
+_sig("bt_sha1_intake_kick", ctypes.c_int, _vp)
+_sig("bt_sha1_intake_sync", ctypes.c_int, _vp)
+_sig("bt_sha1_intake_poll", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
+_sig("bt_sha1_intake_drain", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
+_sig("bt_sha1_intake_pending", _i64, _vp)
+_sig("bt_sha1_intake_get_stats", ctypes.c_int, _vp, ctypes.POINTER(IntakeStats))
+
+
 class ChunkEntry(ctypes.Structure):
     _fields_ = [("id", ctypes.c_int32), ("hash", ctypes.c_uint8 * 20)]
 
@@ -592,6 +611,123 @@ class Receiver:
     def close(self):
         if self.h:
             lib.bt_sha1_receiver_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Intake:
+    """Progressive receive for many chunks at once (bt_sha1_intake_*): advance
+    and commit only record what has arrived, and one kick (poll ends with one)
+    advances every due slot in a single launch."""
+
+    def __init__(self, device=0, chunk_len=CHUNK, nslots=64, stride=0):
+        self.h = lib.bt_sha1_intake_create(device, chunk_len, nslots, stride)
+        if not self.h:
+            raise BtSha1Error(f"bt_sha1_intake_create: {last_error()}")
+        self.chunk_len = chunk_len
+        self.nslots = nslots
+
+    def slot(self):
+        """Hand out a pinned slot (integer address) to receive a chunk into, in order."""
+        p = lib.bt_sha1_intake_slot(self.h)
+        if not p:
+            raise BtSha1Error(f"bt_sha1_intake_slot: {last_error()}")
+        return p
+
+    def advance(self, slot, filled):
+        """Bytes [0, filled) of the slot are final (recorded; nothing is launched)."""
+        _check(lib.bt_sha1_intake_advance(self.h, slot, filled), "bt_sha1_intake_advance")
+
+    def commit(self, slot, expected, tag, length=None):
+        e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
+        _check(lib.bt_sha1_intake_commit(self.h, slot, self.chunk_len if length is None else length, e, tag),
+               "bt_sha1_intake_commit")
+
+    def release(self, slot):
+        _check(lib.bt_sha1_intake_release(self.h, slot), "bt_sha1_intake_release")
+
+    def kick(self):
+        """One launch for every due slot with no launch in flight; the entries launched."""
+        return _check(lib.bt_sha1_intake_kick(self.h), "bt_sha1_intake_kick")
+
+    def sync(self):
+        """Wait for every queued launch; launches nothing."""
+        _check(lib.bt_sha1_intake_sync(self.h), "bt_sha1_intake_sync")
+
+    def receive(self, chunk, expected, tag, piece=1484):
+        """One whole chunk: `piece`-byte payloads in order, advance after each, commit (no kick)."""
+        p = self.slot()
+        data = bytes(chunk)
+        for o in range(0, len(data), piece):
+            part = data[o:o + piece]
+            ctypes.memmove(p + o, part, len(part))
+            self.advance(p, o + len(part))
+        self.commit(p, expected, tag, len(data))
+
+    def receive_all(self, chunks, expected, tags, piece=1484):
+        """All the chunks as an event loop with many downloads delivers them:
+        every turn each chunk in progress gets one `piece`-byte payload in its
+        slot (advance), a complete chunk is committed, and the turn ends with
+        ONE poll.  More chunks than slots wait for a slot.  Returns every
+        verdict."""
+        chunks = [bytes(c) for c in chunks]
+        waiting = list(range(len(chunks)))
+        active, got = [], []  # active: [chunk index, slot, bytes delivered]
+        while waiting or active:
+            while waiting and len(active) < self.nslots:
+                try:
+                    p = self.slot()
+                except BtSha1Error:
+                    break  # every slot is receiving or waits for its verdict: next turn
+                active.append([waiting.pop(0), p, 0])
+            still = []
+            for a in active:
+                k, p, o = a
+                part = chunks[k][o:o + piece]
+                ctypes.memmove(p + o, part, len(part))
+                a[2] = o + len(part)
+                self.advance(p, a[2])
+                if a[2] == len(chunks[k]):
+                    self.commit(p, expected[k], tags[k], a[2])
+                else:
+                    still.append(a)
+            active = still
+            # nothing left to deliver until a slot comes back: wait for the verdicts instead of polling in a loop
+            got += self.poll() if active or not waiting else self.drain()
+        return got + self.drain()
+
+    def _collect(self, fn, max_n=512):
+        out = (Verdict * max_n)()
+        got = _check(fn(self.h, out, max_n), "intake")
+        return [(out[i].tag, bool(out[i].ok), bytes(out[i].digest)) for i in range(got)]
+
+    def poll(self):
+        return self._collect(lib.bt_sha1_intake_poll)
+
+    def drain(self):
+        res = []
+        while True:
+            r = self._collect(lib.bt_sha1_intake_drain)
+            if not r:
+                return res
+            res += r
+
+    def pending(self):
+        return lib.bt_sha1_intake_pending(self.h)
+
+    def stats(self):
+        s = IntakeStats()
+        _check(lib.bt_sha1_intake_get_stats(self.h, ctypes.byref(s)), "bt_sha1_intake_get_stats")
+        return {k: int(getattr(s, k)) for k, _ in IntakeStats._fields_}
+
+    def close(self):
+        if self.h:
+            lib.bt_sha1_intake_destroy(self.h)
             self.h = None
 
     def __del__(self):

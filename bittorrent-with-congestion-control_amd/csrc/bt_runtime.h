@@ -8,6 +8,7 @@
 //   bt_dropin.cpp    sha.h / chunk.h (sha.c:149-163, 453-558; chunk.c:13-83)
 //   bt_verifier.cpp  the batched verifier (util.c:304-337)
 //   bt_receiver.cpp  the progressive receiver (util.c:250-337, hashed while received)
+//   bt_intake.cpp    the same for up to 512 chunks at once, one launch per kick
 // Everything here is in one namespace with hidden visibility: shared between
 // the library's objects, absent from its dynamic symbols.
 #pragma once

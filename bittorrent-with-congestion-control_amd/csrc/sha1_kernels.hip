@@ -914,6 +914,109 @@ __global__ __launch_bounds__(128) void k_sha1_resume(const uint8_t *__restrict__
   }
 }
 
+// ---------------------------------------------------------------------------
+// Table-driven form of the resumable chain kernel, for a host object that
+// advances MANY receive slots in one launch (bt_sha1_intake, bt_intake.cpp).
+// Same S / R split, device helpers, LDS slots and read bound as k_sha1_resume;
+// only where the arguments come from differs.  blockIdx.x = entry w of a table
+// in pinned host memory (BtSha1TableEntry, sha1_launch.h), one two-wave
+// workgroup each, grid 1 .. BTSHA1_TABLE_MAX:
+//   bytes   slots + slot * pitch + from, len of them; no byte at or past
+//           from + len of the slot is read
+//   control block ctl + slot * 128, the receiver's layout: line 0 holds the
+//           chaining state (words 0..4) and the expected hash (bytes 20..39),
+//           line 1 the digest (bytes 64..83), the verdict (byte 84) and the
+//           completion word (word 22)
+//   total == 0  advance: lane 0 of R stores the state back
+//   total != 0  finish of a total-byte chunk: digest and, with VERIFY, the
+//           verdict into the control block; the state is not written back
+// In both cases lane 0 then stores the entry's seq into the slot's completion
+// word, released at system scope after the results.  Whether an entry
+// advances or finishes is workgroup-uniform; barrier accounting as in
+// k_sha1_resume: both waves execute nbatch + 1.
+// ---------------------------------------------------------------------------
+template <bool VERIFY>
+__global__ __launch_bounds__(128) void k_sha1_resume_table(const BtSha1TableEntry *__restrict__ table,
+                                                           const uint8_t *__restrict__ slots, uint64_t pitch,
+                                                           uint8_t *__restrict__ ctl) {
+  __shared__ u32x4 lds[2][kChainStride * kChainBatch];  // as k_sha1_chain: 2 slots x 64 blocks, 42 KiB
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BtSha1TableEntry ent = table[blockIdx.x];
+  const uint8_t *p = slots + (uint64_t)ent.slot * pitch + ent.from;
+  uint8_t *cb = ctl + (uint64_t)ent.slot * BTSHA1_TABLE_CTL;
+  const uint32_t len = ent.len;
+  const uint64_t total = ent.total;
+  const bool fin = total != 0;  // workgroup-uniform: both waves agree
+  const uint64_t nfull = len >> 6;
+  const uint32_t r = len & 63u;
+  const uint64_t nb_total = fin ? nfull + (r >= 56u ? 2u : 1u) : nfull;
+  const uint64_t nbatch = (nb_total + kChainBatch - 1) / kChainBatch;
+  uint32_t *st_io = reinterpret_cast<uint32_t *>(cb);
+  uint32_t nbar = 0;
+  (void)nbar;
+  if (wave == 0) {
+    // ---- S: lane j prepares block b0 + j ----------------------------------
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const uint64_t g = bt * kChainBatch + lane;
+      const uint64_t gc = g < nb_total ? g : nb_total;  // lanes past the end: a block that reads nothing
+      uint32_t w[16];
+      if (fin) chain_block<false>(w, p, gc, nfull, r, total * 8ull);
+      else chain_block<true>(w, p, gc, nfull, 0u, 0ull);
+      produce_wk<0, 80, 1, kChainStride>(w, lds[bt & 1u], lane);
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_BARRIER(nbar);  // pairs with R's last barrier
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+  } else {
+    // ---- R: the chain, from the state the slot's last launch left -----------
+    State st;
+    st.h0 = st_io[0]; st.h1 = st_io[1]; st.h2 = st_io[2]; st.h3 = st_io[3]; st.h4 = st_io[4];
+    BT_LAT_BARRIER(nbar);  // batch 0 is in slot 0
+    const uint32_t l16 = lane & 15u, l4 = lane & 3u;
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const u32x4 *slot = lds[bt & 1u];
+      const uint64_t left = nb_total - bt * kChainBatch;
+      const uint32_t nb = left < kChainBatch ? (uint32_t)left : kChainBatch;
+      // Block k+1's two reads are issued before block k's rounds.
+      u32x4 A = slot[l16], B = slot[16 + l4];
+      for (uint32_t k = 0; k < nb; ++k) {
+        const u32x4 *nxt = slot + (k + 1 < nb ? k + 1 : k) * kChainStride;
+        const u32x4 An = nxt[l16], Bn = nxt[16 + l4];
+        chain_rounds(st, A, B);
+        A = An;
+        B = Bn;
+      }
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+    if (lane == 0) {
+      if (!fin) {
+        st_io[0] = st.h0; st_io[1] = st.h1; st_io[2] = st.h2; st_io[3] = st.h3; st_io[4] = st.h4;
+      } else {
+        const uint32_t h[5] = {st.h0, st.h1, st.h2, st.h3, st.h4};
+        uint8_t *o = cb + 64;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {  // sha.c:550-553
+          o[4 * k] = (uint8_t)(h[k] >> 24);
+          o[4 * k + 1] = (uint8_t)(h[k] >> 16);
+          o[4 * k + 2] = (uint8_t)(h[k] >> 8);
+          o[4 * k + 3] = (uint8_t)h[k];
+        }
+        if constexpr (VERIFY) {  // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+          const uint8_t *x = cb + 20;
+          uint32_t diff = 0;
+#pragma unroll
+          for (int k = 0; k < 20; ++k) diff |= (uint32_t)x[k] ^ ((h[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu);
+          cb[84] = diff == 0;
+        }
+      }
+      // Completion word, as k_sha1_resume's: released at system scope after the results.
+      __hip_atomic_store(reinterpret_cast<uint32_t *>(cb + 88), ent.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 // d_states[5*i ..] = the SHA-1 IV (sha.c:149-163): where k_sha1_resume starts.
 __global__ __launch_bounds__(kBlock) void k_states_init(uint32_t *__restrict__ states, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -1571,6 +1674,16 @@ hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t tot
   else
     hipLaunchKernelGGL(k_sha1_resume<false>, dim3(1), dim3(128), 0, s, (const uint8_t *)data, nullptr, nullptr, nullptr,
                        0ull, len, total, state, digest, expected, ok, done, seq);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_resume_table(const BtSha1TableEntry *table, uint32_t n, const uint8_t *slots, uint64_t pitch,
+                                      uint8_t *ctl, bool verify, hipStream_t s) {
+  if (n == 0 || n > BTSHA1_TABLE_MAX || !table || !slots || !ctl) return hipErrorInvalidValue;
+  if (verify)
+    hipLaunchKernelGGL(k_sha1_resume_table<true>, dim3(n), dim3(128), 0, s, table, slots, pitch, ctl);
+  else
+    hipLaunchKernelGGL(k_sha1_resume_table<false>, dim3(n), dim3(128), 0, s, table, slots, pitch, ctl);
   return hipGetLastError();
 }
 

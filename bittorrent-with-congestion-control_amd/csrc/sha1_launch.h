@@ -87,6 +87,30 @@ BTSHA1_HIDDEN hipError_t btsha1_launch_resume(const void *base, const uint64_t *
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,
                                                   uint8_t *digest, const uint8_t *expected, uint8_t *ok, hipStream_t s,
                                                   uint32_t *done = nullptr, uint32_t seq = 0);
+// The table-driven form (k_sha1_resume_table; bt_intake.cpp): workgroup w
+// serves entry w of `table` (pinned host memory, read with plain loads): bytes
+// [from, from + len) of slot `slot` at slots + slot * pitch, the slot's
+// 128-byte control block at ctl + slot * BTSHA1_TABLE_CTL (chaining state at
+// bytes 0..19, expected hash 20..39, digest 64..83, verdict 84, completion
+// word 88..91).  total == 0 advances the state over the len >> 6 whole blocks;
+// total != 0 finishes a total-byte chunk whose first total - len bytes (a
+// 64-byte multiple) were advanced before, writing the digest and, with verify,
+// the verdict.  Either way `seq` is then stored into the slot's completion
+// word with a system-scope release.  A slot may appear once per launch.
+// hipErrorInvalidValue and no launch for n == 0, n > BTSHA1_TABLE_MAX or a
+// null table, slot base or control base.
+struct alignas(32) BtSha1TableEntry {
+  uint32_t slot;
+  uint32_t from, len;
+  uint32_t total;  // 0: advance; else the chunk's length (at most 32 MiB)
+  uint32_t seq;
+  uint32_t pad[3];
+};
+static_assert(sizeof(BtSha1TableEntry) == 32 && alignof(BtSha1TableEntry) == 32, "table entry layout");
+#define BTSHA1_TABLE_MAX 512u
+#define BTSHA1_TABLE_CTL 128u
+BTSHA1_HIDDEN hipError_t btsha1_launch_resume_table(const BtSha1TableEntry *table, uint32_t n, const uint8_t *slots,
+                                                    uint64_t pitch, uint8_t *ctl, bool verify, hipStream_t s);
 // d_states[5*i ..] = the SHA-1 IV (sha.c:149-163) for i < n.
 BTSHA1_HIDDEN hipError_t btsha1_launch_states_init(uint32_t *d_states, uint64_t n, hipStream_t s);
 // One column of n equal chunks (k_sha1_lat's column forms): chunk i's column

@@ -376,6 +376,65 @@ typedef struct {
 } bt_sha1_receiver_stats;
 int bt_sha1_receiver_get_stats(bt_sha1_receiver *r, bt_sha1_receiver_stats *out);
 
+/* ---- progressive receive for many chunks at once --------------------------- */
+/* The receiver above queues one single-workgroup launch per slot per stride,
+ * so only a handful of chains advance at a time.  The intake has the same slot
+ * life cycle for up to 512 chunks in flight, but advance and commit only
+ * RECORD what has arrived: kick (or poll, which ends with a kick) advances
+ * every slot that is due in ONE launch of the table-driven resumable chain
+ * kernel, one two-wave workgroup per slot.  An event loop calls advance per
+ * payload and poll once per turn.  One thread per object.
+ * nslots: 1..512; chunk_len: 1 .. 32 MiB, and nslots x chunk_len (padded to 64
+ * bytes) at most 2 GiB of pinned memory; stride as in the receiver (0 = 64
+ * KiB; UINT32_MAX = nothing before commit).  NULL with a message for arguments
+ * out of range, before any device call. */
+typedef struct bt_sha1_intake bt_sha1_intake;
+typedef struct {
+  uint64_t kicks;           /* calls to kick (poll's and drain's included)    */
+  uint64_t launches;        /* launches queued                                */
+  uint64_t entries;         /* table entries queued in total                  */
+  uint64_t max_entries;     /* largest single launch                          */
+  uint64_t advanced_bytes;  /* bytes hashed before their chunk's commit       */
+  uint64_t committed;       /* chunks committed                               */
+  uint64_t released;        /* slots released                                 */
+  uint64_t deferred;        /* due slots a kick skipped because their previous
+                               launch was still in flight                     */
+} bt_sha1_intake_stats;
+bt_sha1_intake *bt_sha1_intake_create(int device, uint32_t chunk_len, uint32_t nslots,
+                                      uint32_t stride);
+void bt_sha1_intake_destroy(bt_sha1_intake *r);
+/* As bt_sha1_receiver_slot. */
+uint8_t *bt_sha1_intake_slot(bt_sha1_intake *r);
+/* Bytes [0, filled) of the slot are final; validated as the receiver does.
+ * Records only: once the whole blocks not yet hashed reach `stride` bytes the
+ * slot is due for the next kick. */
+int bt_sha1_intake_advance(bt_sha1_intake *r, uint8_t *slot, uint32_t filled);
+/* The chunk is complete at len bytes (hashed so far <= len <= chunk_len,
+ * len > 0).  Records only: the slot is due, and the next kick that finds it
+ * without a launch in flight queues ONE finishing entry over everything not
+ * yet hashed, with the compare against expected[20] fused. */
+int bt_sha1_intake_commit(bt_sha1_intake *r, uint8_t *slot, uint32_t len,
+                          const uint8_t expected[20], uint64_t tag);
+/* Give an outstanding slot back (aborted download): drops a span that was due
+ * but not launched, waits only for a launch in flight on this slot. */
+int bt_sha1_intake_release(bt_sha1_intake *r, uint8_t *slot);
+/* One launch for every due slot that has no launch in flight; a due slot
+ * whose previous launch has not finished stays due for a later kick.  Returns
+ * the entries launched (0: nothing due), -1 on error.  Does not wait, unless
+ * all of its eight launch tables are still in use (then for the oldest). */
+int bt_sha1_intake_kick(bt_sha1_intake *r);
+/* Wait for every queued launch; launches nothing. */
+int bt_sha1_intake_sync(bt_sha1_intake *r);
+/* Non-blocking: harvests finished chunks from the completion words (no stream
+ * wait), then kicks; copies up to max verdicts out and returns the count. */
+int bt_sha1_intake_poll(bt_sha1_intake *r, bt_sha1_verdict *out, int max);
+/* Blocking: kicks and waits until nothing committed is unfinished, returns up
+ * to max verdicts; -1 if a launch failed. */
+int bt_sha1_intake_drain(bt_sha1_intake *r, bt_sha1_verdict *out, int max);
+/* Verdicts not yet returned (recorded + in flight + finished-unpolled). */
+int64_t bt_sha1_intake_pending(bt_sha1_intake *r);
+int bt_sha1_intake_get_stats(bt_sha1_intake *r, bt_sha1_intake_stats *out);
+
 /* ---- digest lookup (get_chunk_id / find_chunk, util.c:3-39, on the GPU) - */
 /* d_index[q] = smallest i with digest d_table[i] == d_queries[q], else -1.
  * Builds a transient open-addressing table in HBM (stream-ordered alloc). */
