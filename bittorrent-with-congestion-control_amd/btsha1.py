@@ -73,6 +73,7 @@ _sig("bt_sha1_chunks_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp)
 _sig("bt_sha1_verify_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_column_dev", ctypes.c_int, _vp, _u64, _u64, _u64, ctypes.c_int, _vp, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_ragged_dev", ctypes.c_int, _vp, _vp, _vp, _u64, _vp, _vp)
+_sig("bt_sha1_ragged_verify_dev", ctypes.c_int, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_fill_synthetic", ctypes.c_int, _vp, _u64, _u64, _u64, _vp)
 _sig("bt_sha1_chunks_host", _i64, _vp, _u64, _u64, _vp)
 _sig("bt_sha1_host_register", ctypes.c_int, _vp, _u64)
@@ -99,6 +100,14 @@ _sig("bt_sha1_verifier_flush", ctypes.c_int, _vp)
 _sig("bt_sha1_verifier_poll", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
 _sig("bt_sha1_verifier_drain", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
 _sig("bt_sha1_verifier_pending", _i64, _vp)
+
+
+class VerifierStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_verifier_stats
+    _fields_ = [(f, ctypes.c_uint64) for f in ("batches", "ragged_batches", "chunks", "short_chunks", "released")]
+
+
+_sig("bt_sha1_verifier_create_ragged", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+_sig("bt_sha1_verifier_get_stats", ctypes.c_int, _vp, ctypes.POINTER(VerifierStats))
 _sig("bt_sha1_lookup_dev", ctypes.c_int, _vp, _u64, _vp, _u64, _vp, _vp)
 _sig("bt_sha1_states_init_dev", ctypes.c_int, _vp, _u64, _vp)
 _sig("bt_sha1_resume_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
@@ -258,6 +267,14 @@ def column_dev(d_col, n, pitch, width, part, d_state, msg_len=0, d_digests=None,
 
 def ragged_dev(d_base, d_offsets, d_lens, n, d_digests, stream=None):
     _check(lib.bt_sha1_ragged_dev(d_base, d_offsets, d_lens, n, d_digests, stream), "bt_sha1_ragged_dev")
+
+
+def ragged_verify_dev(d_base, d_offsets, d_lens, n, d_expected, d_ok, d_digests=None, stream=None):
+    """ragged_dev with the fused compare: d_ok[i] = 1 iff SHA-1 of message i
+    (d_lens[i] bytes, uint32, at d_base + d_offsets[i], uint64) equals
+    d_expected[20*i ..].  Nothing needs any alignment; d_digests may be None."""
+    _check(lib.bt_sha1_ragged_verify_dev(d_base, d_offsets, d_lens, n, d_expected, d_ok, d_digests, stream),
+           "bt_sha1_ragged_verify_dev")
 
 
 def states_init_dev(d_states, n, stream=None):
@@ -473,13 +490,17 @@ def make_chunks_file(path, chunk_len=CHUNK):
 
 
 class Verifier:
-    """Batched asynchronous verify (bt_sha1_verifier_*)."""
+    """Batched asynchronous verify (bt_sha1_verifier_*).  ragged=True: chunks
+    of any length from 1 to chunk_len (bt_sha1_verifier_create_ragged), e.g. a
+    file's short last chunk; commit / submit then carry the chunk's own length."""
 
-    def __init__(self, device=0, chunk_len=CHUNK, batch=64, nstreams=2):
-        self.h = lib.bt_sha1_verifier_create(device, chunk_len, batch, nstreams)
+    def __init__(self, device=0, chunk_len=CHUNK, batch=64, nstreams=2, ragged=False):
+        create = lib.bt_sha1_verifier_create_ragged if ragged else lib.bt_sha1_verifier_create
+        self.h = create(device, chunk_len, batch, nstreams)
         if not self.h:
-            raise BtSha1Error(f"bt_sha1_verifier_create: {last_error()}")
+            raise BtSha1Error(f"bt_sha1_verifier_create{'_ragged' if ragged else ''}: {last_error()}")
         self.chunk_len = chunk_len
+        self.ragged = ragged
 
     def submit(self, chunk, expected, tag):
         buf, n = _host_buf(chunk)
@@ -528,6 +549,12 @@ class Verifier:
 
     def pending(self):
         return lib.bt_sha1_verifier_pending(self.h)
+
+    def stats(self):
+        """bt_sha1_verifier_get_stats as a dict."""
+        s = VerifierStats()
+        _check(lib.bt_sha1_verifier_get_stats(self.h, ctypes.byref(s)), "bt_sha1_verifier_get_stats")
+        return {k: getattr(s, k) for k, _ in VerifierStats._fields_}
 
     def close(self):
         if self.h:

@@ -408,6 +408,27 @@ int bt_sha1_ragged_dev(const void *d_base, const uint64_t *d_offsets, const uint
   return 0;
 }
 
+int bt_sha1_ragged_verify_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens, uint64_t n,
+                              const uint8_t *d_expected, uint8_t *d_ok, uint8_t *d_digests, void *stream) {
+  if (n == 0) return 0;
+  if (!d_base || !d_offsets || !d_lens || !d_expected || !d_ok) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (n > BTSHA1_RAGGED_VERIFY_MAX) {  // one workgroup per message in the chain form
+    set_err("ragged verify: %llu messages exceed the grid limit of %llu per launch", (unsigned long long)n,
+            (unsigned long long)BTSHA1_RAGGED_VERIFY_MAX);
+    return -1;
+  }
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  DevCtx *c = ctx_for(dev);
+  if (!c) return -1;
+  hipStream_t st = pick_stream(stream);
+  BT_CK(btsha1_launch_ragged_verify(d_base, d_offsets, d_lens, 0, 0, n, d_digests, d_expected, d_ok, st));
+  return 0;
+}
+
 int bt_sha1_states_init_dev(uint32_t *d_states, uint64_t n, void *stream) {
   if (n == 0) return 0;
   if (!d_states) {

@@ -10,6 +10,15 @@
 // (one H2D of its slots, one hot-kernel launch with the fused verify epilogue)
 // once it is closed -- every slot handed out, or flushed -- and each of its
 // handed-out slots has been committed or released.
+//
+// A ragged verifier (bt_sha1_verifier_create_ragged) takes chunks of any
+// length up to max_chunk_len -- a file's short last chunk, the last fread of
+// make_chunks (chunk.c:20).  Its slots lie at a pitch of max_chunk_len rounded
+// up to 16 bytes.  A batch whose committed slots are all max_chunk_len long,
+// with max_chunk_len a 16-byte multiple, launches exactly what a classic
+// verifier launches; any other batch is copied the same way and hashed by ONE
+// btsha1_launch_ragged_verify over (i * pitch, length i), both read by the
+// kernel in place from per-batch pinned arrays, released slots with length 0.
 #include "bt_columns.h"
 #include "bt_runtime.h"
 
@@ -28,6 +37,10 @@ struct VBatch {
   uint32_t *d_state = nullptr;
   StageBuf slots;  // the received chunks: written by the caller, read by the H2D copy
   uint8_t *h_in = nullptr, *h_exp = nullptr, *h_ok = nullptr, *h_dig = nullptr;
+  // ragged verifiers only (pinned, read by the kernel in place): slot i's offset i * pitch and its
+  // committed length (0: released, or not handed out)
+  uint64_t *h_off = nullptr;
+  uint32_t *h_len = nullptr;
   uint8_t *d_in = nullptr;
   std::vector<uint64_t> tags;
   std::vector<uint8_t> state;  // per slot: 0 free, 1 handed out, 2 committed, 3 released
@@ -37,7 +50,10 @@ struct VBatch {
 
 struct bt_sha1_verifier {
   int dev = 0;
-  uint32_t chunk_len = 0, batch = 0;
+  uint32_t chunk_len = 0, batch = 0;  // chunk_len: every chunk's length, or a ragged verifier's max_chunk_len
+  uint32_t pitch = 0;                 // slot i of a batch at i * pitch: chunk_len, rounded up to 16 bytes when ragged
+  bool ragged = false;
+  bt_sha1_verifier_stats st = {};
   std::vector<VBatch> b;
   uint32_t fill = 0;             // batch handing out slots
   std::deque<uint32_t> order;    // batches in flight, oldest first
@@ -89,10 +105,30 @@ int v_launch_columns(bt_sha1_verifier *v, VBatch &b, uint32_t parts) {
   return 0;
 }
 
+// A ragged verifier's batch that needs the ragged launch: a committed slot
+// shorter than max_chunk_len, or slots that are not at a pitch of chunk_len.
+bool v_needs_ragged(const bt_sha1_verifier *v, const VBatch &b) {
+  if (!v->ragged) return false;
+  if (v->pitch != v->chunk_len) return true;
+  for (uint32_t i = 0; i < b.reserved; ++i)
+    if (b.state[i] == 2 && b.h_len[i] != v->chunk_len) return true;
+  return false;
+}
+
 int v_launch(bt_sha1_verifier *v, uint32_t idx) {
   VBatch &b = v->b[idx];
   if (b.reserved == 0) {  // closed while empty: nothing to do
     b.closed = false;
+    return 0;
+  }
+  ++v->st.batches;
+  if (v_needs_ragged(v, b)) {  // one copy, one launch, no column split
+    ++v->st.ragged_batches;
+    BT_CK(hipMemcpyAsync(b.d_in, b.h_in, (size_t)b.reserved * v->pitch, hipMemcpyHostToDevice, b.s));
+    BT_CK(btsha1_launch_ragged_verify(b.d_in, b.h_off, b.h_len, 0, 0, b.reserved, b.h_dig, b.h_exp, b.h_ok, b.s));
+    BT_CK(hipEventRecord(b.ev, b.s));
+    b.inflight = true;
+    v->order.push_back(idx);
     return 0;
   }
   if (const uint32_t parts = v_columns(v->chunk_len, b.reserved)) {
@@ -147,11 +183,11 @@ int v_advance(bt_sha1_verifier *v) {
 int v_locate(bt_sha1_verifier *v, const uint8_t *slot, uint32_t *bi, uint32_t *si) {
   for (uint32_t k = 0; k < v->b.size(); ++k) {
     VBatch &b = v->b[k];
-    if (slot >= b.h_in && slot < b.h_in + (size_t)v->batch * v->chunk_len) {
+    if (slot >= b.h_in && slot < b.h_in + (size_t)v->batch * v->pitch) {
       const size_t off = (size_t)(slot - b.h_in);
-      if (off % v->chunk_len || b.state[off / v->chunk_len] != 1) break;
+      if (off % v->pitch || b.state[off / v->pitch] != 1) break;
       *bi = k;
-      *si = (uint32_t)(off / v->chunk_len);
+      *si = (uint32_t)(off / v->pitch);
       return 0;
     }
   }
@@ -159,15 +195,22 @@ int v_locate(bt_sha1_verifier *v, const uint8_t *slot, uint32_t *bi, uint32_t *s
   return -1;
 }
 
-}  // namespace
-
-extern "C" {
-
-bt_sha1_verifier *bt_sha1_verifier_create(int device, uint32_t chunk_len, uint32_t batch, uint32_t nstreams) {
-  if (chunk_len == 0 || (chunk_len & 15) || chunk_len > (32u << 20) || batch == 0) {
-    set_err("verifier: chunk_len must be a 16-byte multiple <= 32 MiB and batch > 0");
-    return nullptr;
+// The chunk length a commit or a submit brings: exactly chunk_len, or for a
+// ragged verifier anything from 1 to max_chunk_len.
+int v_check_len(const bt_sha1_verifier *v, uint32_t len) {
+  if (v->ragged) {
+    if (len == 0 || len > v->chunk_len) {
+      set_err("verifier: chunk of %u bytes, ragged verifier takes 1 .. %u", len, v->chunk_len);
+      return -1;
+    }
+  } else if (len != v->chunk_len) {
+    set_err("verifier: chunk of %u bytes, verifier built for %u", len, v->chunk_len);
+    return -1;
   }
+  return 0;
+}
+
+bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint32_t nstreams, bool ragged) {
   DevCtx *c = ctx_for(device);
   if (!c) return nullptr;
   KeepDevice keep_dev;
@@ -186,9 +229,11 @@ bt_sha1_verifier *bt_sha1_verifier_create(int device, uint32_t chunk_len, uint32
   auto *v = new bt_sha1_verifier;
   v->dev = device;
   v->chunk_len = chunk_len;
+  v->pitch = ragged ? (chunk_len + 15u) & ~15u : chunk_len;
+  v->ragged = ragged;
   v->batch = batch;
   v->b.resize(std::max<uint32_t>(nstreams, 2));
-  const size_t bytes = (size_t)batch * chunk_len;
+  const size_t bytes = (size_t)batch * v->pitch;
   t_err.clear();
   for (auto &b : v->b) {
     b.tags.resize(batch);
@@ -199,14 +244,41 @@ bt_sha1_verifier *bt_sha1_verifier_create(int device, uint32_t chunk_len, uint32
         hipHostMalloc((void **)&b.h_exp, 20 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&b.h_ok, batch, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&b.h_dig, 20 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&b.d_in, bytes) != hipSuccess) {
+        hipMalloc((void **)&b.d_in, bytes) != hipSuccess ||
+        (ragged && (hipHostMalloc((void **)&b.h_off, 8 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
+                    hipHostMalloc((void **)&b.h_len, 4 * (size_t)batch, hipHostMallocDefault) != hipSuccess))) {
       if (t_err.empty()) set_err("verifier: allocation failed");
       bt_sha1_verifier_destroy(v);
       return nullptr;
     }
     b.h_in = b.slots.as<uint8_t>();
+    for (uint32_t i = 0; ragged && i < batch; ++i) {
+      b.h_off[i] = (uint64_t)i * v->pitch;
+      b.h_len[i] = 0;
+    }
   }
   return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+bt_sha1_verifier *bt_sha1_verifier_create(int device, uint32_t chunk_len, uint32_t batch, uint32_t nstreams) {
+  if (chunk_len == 0 || (chunk_len & 15) || chunk_len > (32u << 20) || batch == 0) {
+    set_err("verifier: chunk_len must be a 16-byte multiple <= 32 MiB and batch > 0");
+    return nullptr;
+  }
+  return v_create(device, chunk_len, batch, nstreams, false);
+}
+
+bt_sha1_verifier *bt_sha1_verifier_create_ragged(int device, uint32_t max_chunk_len, uint32_t batch,
+                                                 uint32_t nstreams) {
+  if (max_chunk_len == 0 || max_chunk_len > (32u << 20) || batch == 0) {
+    set_err("verifier: max_chunk_len must be in [1, 32 MiB] and batch > 0");
+    return nullptr;
+  }
+  return v_create(device, max_chunk_len, batch, nstreams, true);
 }
 
 void bt_sha1_verifier_destroy(bt_sha1_verifier *v) {
@@ -226,6 +298,8 @@ void bt_sha1_verifier_destroy(bt_sha1_verifier *v) {
     if (b.h_exp) (void)hipHostFree(b.h_exp);
     if (b.h_ok) (void)hipHostFree(b.h_ok);
     if (b.h_dig) (void)hipHostFree(b.h_dig);
+    if (b.h_off) (void)hipHostFree(b.h_off);
+    if (b.h_len) (void)hipHostFree(b.h_len);
     if (b.d_in) (void)hipFree(b.d_in);
   }
   delete v;
@@ -240,7 +314,7 @@ uint8_t *bt_sha1_verifier_slot(bt_sha1_verifier *v) {
   const uint32_t j = b.reserved++;
   b.state[j] = 1;
   if (b.reserved == v->batch) b.closed = true;  // launches when its last slot settles
-  return b.h_in + (size_t)j * v->chunk_len;
+  return b.h_in + (size_t)j * v->pitch;
 }
 
 int bt_sha1_verifier_commit(bt_sha1_verifier *v, uint8_t *slot, uint32_t len, const uint8_t expected[20],
@@ -249,16 +323,16 @@ int bt_sha1_verifier_commit(bt_sha1_verifier *v, uint8_t *slot, uint32_t len, co
     set_err("null pointer");
     return -1;
   }
-  if (len != v->chunk_len) {
-    set_err("verifier: chunk of %u bytes, verifier built for %u", len, v->chunk_len);
-    return -1;
-  }
+  if (v_check_len(v, len)) return -1;
   KeepDevice keep_dev;
   if (hipSetDevice(v->dev) != hipSuccess) return -1;
   uint32_t bi, si;
   if (v_locate(v, slot, &bi, &si)) return -1;
   VBatch &b = v->b[bi];
   memcpy(b.h_exp + 20 * (size_t)si, expected, 20);
+  if (v->ragged) b.h_len[si] = len;
+  ++v->st.chunks;
+  if (len < v->chunk_len) ++v->st.short_chunks;
   b.tags[si] = tag;
   b.state[si] = 2;
   ++b.settled;
@@ -277,6 +351,8 @@ int bt_sha1_verifier_release(bt_sha1_verifier *v, uint8_t *slot) {
   if (v_locate(v, slot, &bi, &si)) return -1;
   VBatch &b = v->b[bi];
   memset(b.h_exp + 20 * (size_t)si, 0, 20);
+  if (v->ragged) b.h_len[si] = 0;  // hashed as an empty message; no verdict (v_harvest)
+  ++v->st.released;
   b.state[si] = 3;
   ++b.settled;
   return v_maybe_launch(v, bi);
@@ -288,10 +364,7 @@ int bt_sha1_verifier_submit(bt_sha1_verifier *v, const void *h_chunk, uint32_t l
     set_err("null pointer");
     return -1;
   }
-  if (len != v->chunk_len) {
-    set_err("verifier: chunk of %u bytes, verifier built for %u", len, v->chunk_len);
-    return -1;
-  }
+  if (v_check_len(v, len)) return -1;
   uint8_t *slot = bt_sha1_verifier_slot(v);
   if (!slot) return -1;
   memcpy(slot, h_chunk, len);
@@ -348,5 +421,14 @@ int bt_sha1_verifier_drain(bt_sha1_verifier *v, bt_sha1_verdict *out, int max) {
 }
 
 int64_t bt_sha1_verifier_pending(bt_sha1_verifier *v) { return v ? v->queued : -1; }
+
+int bt_sha1_verifier_get_stats(bt_sha1_verifier *v, bt_sha1_verifier_stats *out) {
+  if (!v || !out) {
+    set_err("null pointer");
+    return -1;
+  }
+  *out = v->st;
+  return 0;
+}
 
 }  // extern "C"

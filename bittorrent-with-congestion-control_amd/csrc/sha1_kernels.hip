@@ -29,6 +29,8 @@
 //   k_sha1_ragged   arbitrary (offset, length) messages and layouts the
 //                   fixed kernels do not take (pitch not a 16-byte multiple,
 //                   offsets past 4 GiB per wave), one message per lane.
+//   k_sha1_lat_ragged_verify / k_sha1_ragged_verify  the two above with the
+//                   fused compare (a short last chunk, util.c:311-313).
 //   k_fill_synthetic  frozen counter-based generator (bench/test data in HBM).
 //   k_lookup_build / k_lookup_query  digest -> first index table in HBM
 //                   (get_chunk_id / find_chunk, util.c:3-39).
@@ -1173,6 +1175,162 @@ __global__ __launch_bounds__(128) void k_sha1_lat_ragged(const uint8_t *__restri
   }
 }
 
+// Digest i as big-endian bytes (sha.c:550-553; byte stores: the ragged kernels
+// promise nothing about the alignment of `digests`) and, with VERIFY, the fused
+// compare of util.c:313 with store_digest<true>'s semantics: ok[i] = 1 iff all
+// 20 bytes equal expected[20*i ..], read bytewise (any alignment).  With VERIFY
+// digests may be NULL.
+template <bool VERIFY>
+__device__ __forceinline__ void store_digest_bytes(const State &st, uint64_t i, uint8_t *digests,
+                                                   const uint8_t *expected, uint8_t *ok) {
+  const uint32_t h[5] = {st.h0, st.h1, st.h2, st.h3, st.h4};
+  if (!VERIFY || digests) {
+    uint8_t *o = digests + i * 20u;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {  // byte stores: digests need no alignment here
+      o[4 * k] = (uint8_t)(h[k] >> 24);
+      o[4 * k + 1] = (uint8_t)(h[k] >> 16);
+      o[4 * k + 2] = (uint8_t)(h[k] >> 8);
+      o[4 * k + 3] = (uint8_t)h[k];
+    }
+  }
+  if constexpr (VERIFY) {  // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+    const uint8_t *x = expected + i * 20u;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) diff |= (uint32_t)x[k] ^ ((h[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu);
+    ok[i] = diff == 0;
+  }
+}
+
+// k_sha1_lat_ragged with the fused compare: ok[i] = digest i == expected[20*i
+// ..] for i < n; digests may be NULL.  The same S and R waves, statement for
+// statement, and the same barrier count, nbmax + SLOTS - 1 each; only R's
+// epilogue differs.  It is a kernel of its own text, not a VERIFY parameter of
+// k_sha1_lat_ragged: that kernel's symbol is pinned (one template argument),
+// and moving its body into a function shared by both reorders its compiled
+// schedule.  Keep the two in step.
+template <int SLOTS>
+__global__ __launch_bounds__(128) void k_sha1_lat_ragged_verify(const uint8_t *__restrict__ base,
+                                                                const uint64_t *__restrict__ offsets,
+                                                                const uint32_t *__restrict__ lens, uint64_t pitch,
+                                                                uint32_t fixed_len, uint64_t n,
+                                                                uint8_t *__restrict__ digests,
+                                                                const uint8_t *__restrict__ expected,
+                                                                uint8_t *__restrict__ ok) {
+  __shared__ u32x4 lds[SLOTS][20 * 64];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t idx = (uint64_t)blockIdx.x * 64u + lane;
+  const uint64_t mi = idx < n ? idx : n - 1;  // lanes past the end re-hash the last message, no store
+  const uint8_t *p = base + (offsets ? offsets[mi] : mi * pitch);
+  const uint32_t len = lens ? lens[mi] : fixed_len;
+  const uint32_t nfull = len >> 6, r = len & 63u;
+  const uint32_t nb = nfull + (r >= 56u ? 2u : 1u);
+  // Both waves hold the same per-lane lengths, so they agree on the trip count
+  // and on the barrier count: nbmax + SLOTS - 1 each.
+  const uint32_t nbmax = __builtin_amdgcn_readfirstlane(wave_max(nb));
+  uint32_t nbar = 0;
+  (void)nbar;
+  if (wave == 0) {
+    // ---- S -------------------------------------------------------------------
+    const uint8_t *lp = nfull ? p : (const uint8_t *)kZeroBlock;
+    const uint32_t lmax = nfull ? nfull - 1u : 0u;
+    const uint64_t bits = (uint64_t)len * 8ull;
+    // The tail bytes + 0x80 (sha.c:536-538) are read once, up front: a load in
+    // the per-block lane-divergent branch below would make the compiler wait
+    // for the whole prefetch ring at the branch join on every block.
+    uint32_t tw[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) tw[j] = 0u;
+    {
+      const uint8_t *t = p + 64u * nfull;
+      for (uint32_t q = 0; q < r; ++q) tw[q >> 2] |= (uint32_t)t[q] << (24 - 8 * (q & 3));
+      tw[r >> 2] |= 0x80000000u >> ((r & 3) * 8);
+    }
+    uint32_t slot = 0;
+    u32x4 ring[4][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) __builtin_memcpy(&ring[k][i], lp + 64u * ((uint32_t)k < lmax ? k : lmax) + 16 * i, 16);
+    for (uint32_t b = 0; b < nbmax; b += 4) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t nx = b + k + 3u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) __builtin_memcpy(&ring[(k + 3) % 4][i], lp + 64u * (nx < lmax ? nx : lmax) + 16 * i, 16);
+        __builtin_amdgcn_sched_barrier(0);
+        const uint32_t bk = b + k;
+        if (bk < nbmax) {  // wave-uniform
+          uint32_t w[16];
+          if (bk < nfull) {
+            block_from_le(w, ring[k][0], ring[k][1], ring[k][2], ring[k][3]);
+          } else {  // the tail block, then (r >= 56) a length-only block, sha.c:536-543
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w[j] = bk == nfull ? tw[j] : 0u;
+            if ((bk == nfull && r < 56u) || bk == nfull + 1u) {
+              w[14] = (uint32_t)(bits >> 32);
+              w[15] = (uint32_t)bits;
+            }
+          }
+          produce_block<SLOTS>(w, lds, slot, lane, nbar);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SLOTS - 1; ++k) BT_LAT_BARRIER(nbar);  // pair with R's last barriers
+    BT_LAT_CHECK(nbar, nbmax + SLOTS - 1u);
+  } else {
+    // ---- R -------------------------------------------------------------------
+    State st, fin;
+    st.init();
+    fin = st;
+    auto latch = [&](uint32_t b) {  // this lane's last block done: keep its state
+      if (b + 1u == nb) fin = st;
+    };
+    if constexpr (SLOTS == 2) {
+      BT_LAT_BARRIER(nbar);
+      for (uint32_t b = 0; b < nbmax; ++b) {
+        uint32_t a = st.h0, bb = st.h1, c = st.h2, d = st.h3, e = st.h4;
+        consume_wk<0, 80>(a, bb, c, d, e, lds[b & 1u], lane);
+        BT_LAT_BARRIER(nbar);
+        st.h0 += a;  // sha.c:446-450
+        st.h1 += bb;
+        st.h2 += c;
+        st.h3 += d;
+        st.h4 += e;
+        latch(b);
+      }
+    } else {
+      BT_LAT_BARRIER(nbar);
+      BT_LAT_BARRIER(nbar);
+      u32x4 wa[20], wb[20];
+      lat_fetch(wa, lds[0], lane);
+      uint32_t sb = 0;
+      for (uint32_t b = 0; b < nbmax; b += 2) {
+        const uint32_t s1 = sb + 1u == 3u ? 0u : sb + 1u;
+        const uint32_t s2 = s1 + 1u == 3u ? 0u : s1 + 1u;
+        lat_fetch(wb, lds[b + 1 < nbmax ? s1 : sb], lane);
+        lat_rounds(st, wa);
+        latch(b);
+        BT_LAT_BARRIER(nbar);
+        if (b + 1 < nbmax) {
+          lat_fetch(wa, lds[b + 2 < nbmax ? s2 : s1], lane);
+          lat_rounds(st, wb);
+          latch(b + 1);
+          BT_LAT_BARRIER(nbar);
+        }
+        sb = s2;
+      }
+    }
+    BT_LAT_CHECK(nbar, nbmax + SLOTS - 1u);
+    // The fused compare belongs to R's epilogue, after the barrier check: it
+    // adds no barrier.  Lanes past n write neither a digest nor a verdict.
+    if (idx < n) store_digest_bytes<true>(fin, idx, digests, expected, ok);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Generic paths (64-bit addressing, any alignment).
 // ---------------------------------------------------------------------------
@@ -1249,12 +1407,14 @@ __device__ __forceinline__ void absorb_tail_and_finish(State &st, const uint8_t 
 }
 
 // Message i = base[offsets[i] .. + lens[i]); with offsets == NULL the batch is
-// strided instead: message i = base[i*pitch .. + fixed_len).
-__global__ __launch_bounds__(kBlock) void k_sha1_ragged(const uint8_t *__restrict__ base,
-                                                        const uint64_t *__restrict__ offsets,
-                                                        const uint32_t *__restrict__ lens, uint64_t pitch,
-                                                        uint32_t fixed_len, uint64_t n,
-                                                        uint8_t *__restrict__ digests) {
+// strided instead: message i = base[i*pitch .. + fixed_len).  VERIFY: the lane
+// that owns message i also writes ok[i] = digest i == expected[20*i ..];
+// lanes past n return before any store.
+template <bool VERIFY = false>
+__device__ __forceinline__ void ragged_body(const uint8_t *__restrict__ base, const uint64_t *__restrict__ offsets,
+                                            const uint32_t *__restrict__ lens, uint64_t pitch, uint32_t fixed_len,
+                                            uint64_t n, uint8_t *__restrict__ digests,
+                                            const uint8_t *__restrict__ expected, uint8_t *__restrict__ ok) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint8_t *p = base + (offsets ? offsets[i] : i * pitch);
@@ -1264,15 +1424,26 @@ __global__ __launch_bounds__(kBlock) void k_sha1_ragged(const uint8_t *__restric
   const uint64_t nb = len >> 6;
   absorb_blocks(st, p, nb);
   absorb_tail_and_finish(st, p + nb * 64u, len & 63u, len);
-  uint8_t *o = digests + i * 20u;
-  const uint32_t h[5] = {st.h0, st.h1, st.h2, st.h3, st.h4};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {  // byte stores: digests need no alignment here
-    o[4 * k] = (uint8_t)(h[k] >> 24);
-    o[4 * k + 1] = (uint8_t)(h[k] >> 16);
-    o[4 * k + 2] = (uint8_t)(h[k] >> 8);
-    o[4 * k + 3] = (uint8_t)h[k];
-  }
+  store_digest_bytes<VERIFY>(st, i, digests, expected, ok);
+}
+
+__global__ __launch_bounds__(kBlock) void k_sha1_ragged(const uint8_t *__restrict__ base,
+                                                        const uint64_t *__restrict__ offsets,
+                                                        const uint32_t *__restrict__ lens, uint64_t pitch,
+                                                        uint32_t fixed_len, uint64_t n,
+                                                        uint8_t *__restrict__ digests) {
+  ragged_body(base, offsets, lens, pitch, fixed_len, n, digests, nullptr, nullptr);
+}
+
+// The VERIFY = true form (digests may be NULL), as k_sha1_lat_ragged_verify.
+__global__ __launch_bounds__(kBlock) void k_sha1_ragged_verify(const uint8_t *__restrict__ base,
+                                                               const uint64_t *__restrict__ offsets,
+                                                               const uint32_t *__restrict__ lens, uint64_t pitch,
+                                                               uint32_t fixed_len, uint64_t n,
+                                                               uint8_t *__restrict__ digests,
+                                                               const uint8_t *__restrict__ expected,
+                                                               uint8_t *__restrict__ ok) {
+  ragged_body<true>(base, offsets, lens, pitch, fixed_len, n, digests, expected, ok);
 }
 
 // ---------------------------------------------------------------------------
@@ -1614,6 +1785,37 @@ hipError_t btsha1_launch_ragged(const void *d_base, const uint64_t *d_off, const
   const uint64_t grid = (n + wg - 1) / wg;
   hipLaunchKernelGGL(k_sha1_ragged, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)d_base, d_off,
                      d_len, pitch, fixed_len, n, d_dig);
+  return hipGetLastError();
+}
+
+// btsha1_launch_ragged with the fused compare: the same three-way choice by n,
+// every form writing ok[i] for i < n and nothing else past the digests.
+hipError_t btsha1_launch_ragged_verify(const void *d_base, const uint64_t *d_off, const uint32_t *d_len, uint64_t pitch,
+                                       uint32_t fixed_len, uint64_t n, uint8_t *d_dig, const uint8_t *d_exp,
+                                       uint8_t *d_ok, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!d_base || !d_exp || !d_ok || !d_off != !d_len || n > BTSHA1_RAGGED_VERIFY_MAX) return hipErrorInvalidValue;
+  // k_sha1_chain<false, true> takes offsets and lengths as it stands; only
+  // btsha1_launch_chain, whose callers verify whole chunks, refuses them.
+  if (n <= btsha1_chain_batch()) {
+    hipLaunchKernelGGL((k_sha1_chain<false, true>), dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)d_base, d_off,
+                       d_len, pitch, (uint64_t)fixed_len, 0ull, nullptr, d_dig, d_exp, d_ok, nullptr, 0u);
+    return hipGetLastError();
+  }
+  if (n <= btsha1_latency_batch()) {
+    const uint64_t grid = (n + 63) / 64;
+    if (grid > btsha1_device_cus())
+      hipLaunchKernelGGL(k_sha1_lat_ragged_verify<3>, dim3((uint32_t)grid), dim3(128), 0, s, (const uint8_t *)d_base,
+                         d_off, d_len, pitch, fixed_len, n, d_dig, d_exp, d_ok);
+    else
+      hipLaunchKernelGGL(k_sha1_lat_ragged_verify<2>, dim3((uint32_t)grid), dim3(128), 0, s, (const uint8_t *)d_base,
+                         d_off, d_len, pitch, fixed_len, n, d_dig, d_exp, d_ok);
+    return hipGetLastError();
+  }
+  const uint32_t wg = chain_workgroup(n);
+  const uint64_t grid = (n + wg - 1) / wg;
+  hipLaunchKernelGGL(k_sha1_ragged_verify, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)d_base, d_off, d_len,
+                     pitch, fixed_len, n, d_dig, d_exp, d_ok);
   return hipGetLastError();
 }
 

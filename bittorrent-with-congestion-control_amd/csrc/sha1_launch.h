@@ -82,6 +82,18 @@ BTSHA1_HIDDEN hipError_t btsha1_launch_resume(const void *base, const uint64_t *
                                               const uint64_t *totals, uint64_t n, uint32_t *states, uint8_t *digests,
                                               const uint8_t *expected, uint8_t *ok, hipStream_t s,
                                               uint32_t *done = nullptr, uint32_t seq = 0);
+// btsha1_launch_ragged with the fused compare (k_sha1_chain<false, true>,
+// k_sha1_lat_ragged_verify<2 / 3>, k_sha1_ragged_verify: the same choice by n,
+// under the same two settings): d_ok[i] = digest i == d_exp[20*i ..]
+// (util.c:313) for i < n.  d_exp, d_ok and d_dig take any alignment and may be
+// device or pinned host memory; d_dig may be NULL.  d_off and d_len come
+// together or not at all.  hipErrorInvalidValue and no launch for a null
+// d_base, d_exp or d_ok, one of d_off / d_len without the other, or n above
+// BTSHA1_RAGGED_VERIFY_MAX (the grid of the one-workgroup-per-message form).
+#define BTSHA1_RAGGED_VERIFY_MAX 0x7fffffffull
+BTSHA1_HIDDEN hipError_t btsha1_launch_ragged_verify(const void *d_base, const uint64_t *d_off, const uint32_t *d_len,
+                                                     uint64_t pitch, uint32_t fixed_len, uint64_t n, uint8_t *d_dig,
+                                                     const uint8_t *d_exp, uint8_t *d_ok, hipStream_t s);
 // The single-message form (grid 1): offset, length and total are kernel
 // arguments, so a host object launches it with no device-side arrays.
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,

@@ -28,6 +28,12 @@
  * one round always leaves round 0 untimed (it lands the data in the slots).
  * The last line is a JSON summary with the host->verdict rate of the timed
  * rounds.
+ *
+ * A data file whose size is no multiple of BT_CHUNK_SIZE ends in a short chunk
+ * (the last fread of make_chunks, chunk.c:20), for which make-chunks writes a
+ * digest like for any other.  That chunk is received and committed at its own
+ * length, in every mode, and the verifiers are then ragged ones
+ * (bt_sha1_verifier_create_ragged); for a whole-multiple file nothing changes.
  */
 #include <fcntl.h>
 #include <pthread.h>
@@ -102,6 +108,7 @@ struct shared {
   const uint8_t *img;
   const int *ids;
   const uint8_t *exp;
+  const uint32_t *len; /* bytes of chunk k: BT_CHUNK_SIZE, less for the file's short last chunk */
   int corrupt, zcopy, poll_every, rounds, warm;
   long ring;
   pthread_barrier_t *bar; /* -t: the lanes meet after the warm-up rounds */
@@ -117,6 +124,7 @@ struct lane {
   struct resident *res; /* -z: which chunk each of its pinned slots holds */
   long nres;
   long good, bad, total, timed, late_fills, commits;
+  uint64_t timed_bytes;
   int err;
   const struct shared *sh;
 };
@@ -174,18 +182,22 @@ static int receive_one(struct lane *l, int r, long i) {
   }
   if (!sh->zcopy || r == 0 || fill) {
     const uint64_t off = (uint64_t)sh->ids[k] * BT_CHUNK_SIZE;
-    for (uint32_t got = 0; got < BT_CHUNK_SIZE; got += PAYLOAD) { /* save_data_packet, util.c:275 */
-      uint32_t len = BT_CHUNK_SIZE - got < PAYLOAD ? BT_CHUNK_SIZE - got : PAYLOAD;
+    const uint32_t clen = sh->len[k];
+    for (uint32_t got = 0; got < clen; got += PAYLOAD) { /* save_data_packet, util.c:275 */
+      uint32_t len = clen - got < PAYLOAD ? clen - got : PAYLOAD;
       memcpy(slot + got, sh->img + off + got, len);
     }
-    if (sh->corrupt && k % 7 == 3) slot[k % BT_CHUNK_SIZE] ^= 0x5a;
+    if (sh->corrupt && k % 7 == 3) slot[k % clen] ^= 0x5a;
   }
-  if (bt_sha1_verifier_commit(l->v, slot, BT_CHUNK_SIZE, sh->exp + 20 * k, (uint64_t)k)) {
+  if (bt_sha1_verifier_commit(l->v, slot, sh->len[k], sh->exp + 20 * k, (uint64_t)k)) {
     fprintf(stderr, "verify-stream: %s\n", bt_sha1_last_error());
     return -1;
   }
   l->total++;
-  if (r >= sh->warm) l->timed++;
+  if (r >= sh->warm) {
+    l->timed++;
+    l->timed_bytes += sh->len[k];
+  }
   if (++l->commits % sh->poll_every == 0 && drain_lane(l, 0)) return -1;
   return 0;
 }
@@ -276,12 +288,17 @@ int main(int argc, char **argv) {
   }
   fclose(cf);
 
-  /* only whole chunks are verified (util.c:307) */
-  int m0 = 0;
+  /* every listed chunk that starts inside the file: whole ones (util.c:307)
+   * and the short one the file ends in */
+  uint32_t *clen = malloc(sizeof(uint32_t) * (n ? n : 1));
+  int m0 = 0, any_short = 0;
   for (int k = 0; k < n; k++)
-    if (ids[k] >= 0 && (uint64_t)ids[k] * BT_CHUNK_SIZE + BT_CHUNK_SIZE <= (uint64_t)st.st_size) {
+    if (ids[k] >= 0 && (uint64_t)ids[k] * BT_CHUNK_SIZE < (uint64_t)st.st_size) {
+      const uint64_t left = (uint64_t)st.st_size - (uint64_t)ids[k] * BT_CHUNK_SIZE;
       ids[m0] = ids[k];
       memcpy(exp + 20 * m0, exp + 20 * k, 20);
+      clen[m0] = left < BT_CHUNK_SIZE ? (uint32_t)left : BT_CHUNK_SIZE;
+      if (clen[m0] < BT_CHUNK_SIZE) any_short = 1;
       m0++;
     }
   n = m0;
@@ -295,13 +312,14 @@ int main(int argc, char **argv) {
   }
   double t0 = 0;
   pthread_barrier_t bar;
-  struct shared sh = {img, ids, exp, corrupt, zcopy, poll_every, rounds, warm,
+  struct shared sh = {img, ids, exp, clen, corrupt, zcopy, poll_every, rounds, warm,
                       (long)batch * (streams < 2 ? 2 : streams), &bar, &t0};
   struct lane *L = calloc((size_t)G, sizeof *L);
   long per_round_max = 0;
   for (int g = 0; g < G; g++) {
     L[g].sh = &sh;
-    L[g].v = bt_sha1_verifier_create(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams);
+    L[g].v = any_short ? bt_sha1_verifier_create_ragged(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams)
+                       : bt_sha1_verifier_create(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams);
     if (!L[g].v) {
       fprintf(stderr, "verify-stream: %s\n", bt_sha1_last_error());
       return 255;
@@ -355,21 +373,24 @@ int main(int argc, char **argv) {
   if (err) return 255;
   double dt = now() - t0;
   long good = 0, bad = 0, total = 0, timed = 0, late = 0;
+  uint64_t timed_bytes = 0;
   for (int g = 0; g < G; g++) {
     good += L[g].good;
     bad += L[g].bad;
     total += L[g].total;
     timed += L[g].timed;
+    timed_bytes += L[g].timed_bytes;
     late += L[g].late_fills;
     bt_sha1_verifier_destroy(L[g].v);
     free(L[g].ks);
     free(L[g].res);
   }
   free(L);
+  free(clen);
   printf("{\"chunks\": %ld, \"ok\": %ld, \"failed\": %ld, \"seconds\": %.6f, \"GiB_per_s\": %.4f, \"batch\": %d, "
          "\"streams\": %d, \"poll_every\": %d, \"verifiers\": %d, \"devices\": %d, \"receive_threads\": %d, "
          "\"rounds\": %d, \"warmup_rounds\": %d, \"timed_chunks\": %ld, \"late_fills\": %ld, \"mode\": \"%s\"}\n",
-         total, good, bad, dt, timed * (double)BT_CHUNK_SIZE / dt / (1u << 30), batch, streams, poll_every, G,
+         total, good, bad, dt, (double)timed_bytes / dt / (1u << 30), batch, streams, poll_every, G,
          G < ndev ? G : ndev, threads ? G : 1, rounds, warm, timed, late,
          zcopy ? "zero-copy slots" : "packetized memcpy (util.c:275)");
   return bad && !corrupt ? 1 : 0;

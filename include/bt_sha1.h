@@ -147,6 +147,18 @@ int bt_sha1_verify_dev(const void *d_in, uint64_t n, uint64_t chunk_len, uint64_
 /* n messages, message i = d_base[d_offsets[i] .. + d_lens[i]). */
 int bt_sha1_ragged_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
                        uint64_t n, uint8_t *d_digests, void *stream);
+/* Same, then compares with d_expected (20*n): d_ok[i] = 1 iff digest i equals
+ * d_expected[20*i .. 20*i+19], else 0 (util.c:311-313) -- the verify form for
+ * chunks of any length at any offset, e.g. a file's short last chunk (the last
+ * fread of make_chunks, chunk.c:20), which bt_sha1_verify_dev does not take.
+ * d_expected, d_ok and d_digests take any alignment; d_digests may be NULL.
+ * The batch size selects the kernel as for bt_sha1_ragged_dev, under
+ * bt_sha1_set_chain_batch and bt_sha1_set_latency_batch.  n == 0 is no work;
+ * a null d_base / d_offsets / d_lens / d_expected / d_ok, or n above 2^31 - 1
+ * (the grid), are -1 before any device call. */
+int bt_sha1_ragged_verify_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
+                              uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
+                              uint8_t *d_digests /* may be NULL */, void *stream);
 /* Resumable hashing of messages that are still arriving (a peer appends a
  * chunk's payloads in order, util.c:275, and hashes it only when complete,
  * util.c:311-313; SHA-1 resumes at every 64-byte boundary).  This is the
@@ -301,13 +313,28 @@ typedef struct {
  * H2D of batch k+1 with hashing of batch k); chunk_len: BT_CHUNK_SIZE. */
 bt_sha1_verifier *bt_sha1_verifier_create(int device, uint32_t chunk_len, uint32_t batch,
                                           uint32_t nstreams);
+/* A verifier for chunks of ANY length from 1 to max_chunk_len (1 .. 32 MiB, any
+ * value): a file's short last chunk (the last fread of make_chunks,
+ * chunk.c:20) is committed at its own length, like the receiver and the intake
+ * take it.  Slots lie at a pitch of max_chunk_len rounded up to 16 bytes.  A
+ * batch whose committed chunks are all max_chunk_len long, with max_chunk_len a
+ * 16-byte multiple, launches exactly what the verifier above launches (the hot
+ * kernel, or the column split); any other batch is copied the same way and
+ * hashed by one launch of the ragged kernels with the compare fused (as
+ * bt_sha1_ragged_verify_dev; no column split).  NULL with a message for
+ * arguments out of range, before any device call.  Everything below works on
+ * both kinds; a verifier from bt_sha1_verifier_create still refuses any len
+ * but chunk_len. */
+bt_sha1_verifier *bt_sha1_verifier_create_ragged(int device, uint32_t max_chunk_len, uint32_t batch,
+                                                 uint32_t nstreams);
 void bt_sha1_verifier_destroy(bt_sha1_verifier *v);
 /* Zero-copy: hand out a pinned chunk_len-byte slot to assemble one chunk in
  * (e.g. save_data_packet's memcpy target, util.c:275).  Several slots may be
  * outstanding (one per in-progress download); blocks only when the ring must
  * wrap onto a batch still in flight.  NULL on error. */
 uint8_t *bt_sha1_verifier_slot(bt_sha1_verifier *v);
-/* Queue an outstanding slot for verification against expected[20]. */
+/* Queue an outstanding slot for verification against expected[20].  len is
+ * chunk_len; for a ragged verifier, the chunk's own length, 1 .. max_chunk_len. */
 int bt_sha1_verifier_commit(bt_sha1_verifier *v, uint8_t *slot, uint32_t len,
                             const uint8_t expected[20], uint64_t tag);
 /* Give an outstanding slot back unverified (aborted download); no verdict. */
@@ -323,6 +350,17 @@ int bt_sha1_verifier_poll(bt_sha1_verifier *v, bt_sha1_verdict *out, int max);
 int bt_sha1_verifier_drain(bt_sha1_verifier *v, bt_sha1_verdict *out, int max);
 /* Verdicts not yet returned (in flight + finished-unpolled). */
 int64_t bt_sha1_verifier_pending(bt_sha1_verifier *v);
+typedef struct {
+  uint64_t batches;         /* batches launched                               */
+  uint64_t ragged_batches;  /* of them, through the ragged kernels: a short
+                               chunk in the batch, or max_chunk_len not a
+                               16-byte multiple (always 0 for a verifier from
+                               bt_sha1_verifier_create)                       */
+  uint64_t chunks;          /* chunks committed                               */
+  uint64_t short_chunks;    /* of them, shorter than max_chunk_len            */
+  uint64_t released;        /* slots released                                 */
+} bt_sha1_verifier_stats;
+int bt_sha1_verifier_get_stats(bt_sha1_verifier *v, bt_sha1_verifier_stats *out);
 
 /* ---- progressive receive (util.c:250-337 for in-order delivery) ---------- */
 /* The verifier above starts a chunk's serial chain when its last byte has
