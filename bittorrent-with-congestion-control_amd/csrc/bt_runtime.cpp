@@ -499,12 +499,14 @@ int bt_sha1_host_unregister(void *h_ptr) {
 int bt_sha1_lookup_dev(const uint8_t *d_table, uint64_t n_table, const uint8_t *d_queries, uint64_t n_queries,
                        int64_t *d_index, void *stream) {
   if (n_queries == 0) return 0;
-  if ((n_table && !d_table) || !d_queries || !d_index || ((uintptr_t)d_table & 3) || ((uintptr_t)d_queries & 3)) {
-    set_err("lookup needs non-null, 4-byte aligned digest arrays");
+  // cap below is a uint32_t of at least 2 * n_table: past 2^30 entries it
+  // would have to be 2^32, and the doubling loop would wrap to 0 and never end.
+  if (n_table > (1ull << 30)) {
+    set_err("lookup table too large");
     return -1;
   }
-  if (n_table >= (1ull << 31)) {
-    set_err("lookup table too large");
+  if ((n_table && !d_table) || !d_queries || !d_index || ((uintptr_t)d_table & 3) || ((uintptr_t)d_queries & 3)) {
+    set_err("lookup needs non-null, 4-byte aligned digest arrays");
     return -1;
   }
   int dev = 0;

@@ -475,7 +475,11 @@ int bt_sha1_intake_get_stats(bt_sha1_intake *r, bt_sha1_intake_stats *out);
 
 /* ---- digest lookup (get_chunk_id / find_chunk, util.c:3-39, on the GPU) - */
 /* d_index[q] = smallest i with digest d_table[i] == d_queries[q], else -1.
- * Builds a transient open-addressing table in HBM (stream-ordered alloc). */
+ * Builds a transient open-addressing table in HBM (stream-ordered alloc):
+ * a power of two of at least 2 * n_table 32-bit slots, at least 1024.
+ * n_table is at most 2^30 (the slot count is a uint32_t: 2^31 slots, 8 GiB);
+ * a larger table is refused with -1 and "lookup table too large" before any
+ * device call.  Both digest arrays are 4-byte aligned. */
 int bt_sha1_lookup_dev(const uint8_t *d_table, uint64_t n_table, const uint8_t *d_queries,
                        uint64_t n_queries, int64_t *d_index, void *stream);
 
