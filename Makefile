@@ -11,7 +11,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude -I$(CSRC
 # includes), so a comment-only edit keeps the id and the profiles tied to it.
 # Any gcc failure or an empty result falls back to hashing the raw files
 # (prefix "raw-"), so a broken strip can never alias every build to one id.
-KSRC     := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h
+KSRC     := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_gather_walk.h
 SRC_ID   := $(shell out=$$(for f in $(KSRC); do gcc -fpreprocessed -dD -E -P -x c++ $$f 2>/dev/null || exit 1; done) \
               && [ -n "$$out" ] && printf '%s\n' "$$out" | sha256sum | cut -c1-16)
 ifeq ($(strip $(SRC_ID)),)
@@ -31,7 +31,7 @@ lib: $(LIB)
 # variant but asan (which instruments all host code) links the product's.
 HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_receiver bt_intake bt_chunks
 HOSTOBJ  := $(HOST:%=$(PKG)/build/%.o)
-KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h
+KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/sha1_gather_walk.h
 HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/sha.h include/chunk.h
 SONAME   := -Wl,-soname,libbtsha1.so
 # One build of the library: $(call libbtsha1,object dir,library,kernel flags,
@@ -105,6 +105,15 @@ $(ASANDIR)/host_stress: tests/native/host_stress.c $(ASANDIR)/libbtsha1.so
 	/opt/rocm/llvm/bin/clang -gline-tables-only -O1 -fsanitize=address,undefined -shared-libasan -fno-omit-frame-pointer -Iinclude -o $@ $< \
 	    -L$(ASANDIR) -lbtsha1 -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(ASANRT)
 
+# The gather kernels' block walk (sha1_gather_walk.h) run on the CPU under
+# ASan/UBSan, every segment an allocation of its own: a stand-alone program,
+# built and run by tests/test_gather_walk_host.py too.
+WALKDIR  := build_variants/gather_walk
+gather_walk_check: $(WALKDIR)/gather_walk_check
+$(WALKDIR)/gather_walk_check: tests/native/gather_walk_check.cpp $(CSRC)/sha1_gather_walk.h
+	@mkdir -p $(WALKDIR)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
+
 # Barrier-accounting build: the latency / chain / ragged-latency kernels count
 # the s_barriers each wave executes and check them against the invariant they
 # rely on (sha1_kernels.hip, "Barrier accounting"); bt_sha1_debug_barrier_stats
@@ -162,4 +171,4 @@ clean:
 	rm -rf $(PKG)/build $(LIB) $(BIN)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib tools oracle dropin asan dbgbar experiments ubench sched_variants install clean
+.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check ubench sched_variants install clean

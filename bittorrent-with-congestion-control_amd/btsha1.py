@@ -108,6 +108,23 @@ class VerifierStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_verifier_sta
 
 _sig("bt_sha1_verifier_create_ragged", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
 _sig("bt_sha1_verifier_get_stats", ctypes.c_int, _vp, ctypes.POINTER(VerifierStats))
+
+
+class Seg(ctypes.Structure):  # include/bt_sha1.h bt_sha1_seg
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class VerifierGatherStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_verifier_gather_stats
+    _fields_ = [(f, ctypes.c_uint64) for f in ("gather_batches", "gather_chunks", "segments", "payload_bytes",
+                                               "copied_bytes")]
+
+
+_sig("bt_sha1_gather_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp)
+_sig("bt_sha1_gather_verify_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
+_sig("bt_sha1_verifier_create_gather", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+     ctypes.c_uint32)
+_sig("bt_sha1_verifier_commit_gather", ctypes.c_int, _vp, _vp, ctypes.POINTER(Seg), ctypes.c_uint32, _vp, _u64)
+_sig("bt_sha1_verifier_get_gather_stats", ctypes.c_int, _vp, ctypes.POINTER(VerifierGatherStats))
 _sig("bt_sha1_lookup_dev", ctypes.c_int, _vp, _u64, _vp, _u64, _vp, _vp)
 _sig("bt_sha1_states_init_dev", ctypes.c_int, _vp, _u64, _vp)
 _sig("bt_sha1_resume_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
@@ -275,6 +292,19 @@ def ragged_verify_dev(d_base, d_offsets, d_lens, n, d_expected, d_ok, d_digests=
     d_expected[20*i ..].  Nothing needs any alignment; d_digests may be None."""
     _check(lib.bt_sha1_ragged_verify_dev(d_base, d_offsets, d_lens, n, d_expected, d_ok, d_digests, stream),
            "bt_sha1_ragged_verify_dev")
+
+
+def gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, stream=None):
+    """Message i = the concatenation of the d_seg_count[i] (uint32) segments
+    d_segs[d_seg_first[i] (uint64) ..], each a Seg: len bytes at d_base + off."""
+    _check(lib.bt_sha1_gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, stream),
+           "bt_sha1_gather_dev")
+
+
+def gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d_ok, d_digests=None, stream=None):
+    """gather_dev with the fused compare, as ragged_verify_dev."""
+    _check(lib.bt_sha1_gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d_ok, d_digests,
+                                         stream), "bt_sha1_gather_verify_dev")
 
 
 def states_init_dev(d_states, n, stream=None):
@@ -492,15 +522,23 @@ def make_chunks_file(path, chunk_len=CHUNK):
 class Verifier:
     """Batched asynchronous verify (bt_sha1_verifier_*).  ragged=True: chunks
     of any length from 1 to chunk_len (bt_sha1_verifier_create_ragged), e.g. a
-    file's short last chunk; commit / submit then carry the chunk's own length."""
+    file's short last chunk; commit / submit then carry the chunk's own length.
+    gather=True: the slots hold datagrams (bt_sha1_verifier_create_gather);
+    chunk_len is the slot length, max_segs the most segments commit_gather lists."""
 
-    def __init__(self, device=0, chunk_len=CHUNK, batch=64, nstreams=2, ragged=False):
-        create = lib.bt_sha1_verifier_create_ragged if ragged else lib.bt_sha1_verifier_create
-        self.h = create(device, chunk_len, batch, nstreams)
+    def __init__(self, device=0, chunk_len=CHUNK, batch=64, nstreams=2, ragged=False, gather=False, max_segs=0):
+        if gather:
+            self.h = lib.bt_sha1_verifier_create_gather(device, chunk_len, max_segs, batch, nstreams)
+        else:
+            create = lib.bt_sha1_verifier_create_ragged if ragged else lib.bt_sha1_verifier_create
+            self.h = create(device, chunk_len, batch, nstreams)
         if not self.h:
-            raise BtSha1Error(f"bt_sha1_verifier_create{'_ragged' if ragged else ''}: {last_error()}")
+            kind = "_gather" if gather else "_ragged" if ragged else ""
+            raise BtSha1Error(f"bt_sha1_verifier_create{kind}: {last_error()}")
         self.chunk_len = chunk_len
         self.ragged = ragged
+        self.gather = gather
+        self.max_segs = max_segs
 
     def submit(self, chunk, expected, tag):
         buf, n = _host_buf(chunk)
@@ -518,6 +556,13 @@ class Verifier:
         e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
         _check(lib.bt_sha1_verifier_commit(self.h, slot, length or self.chunk_len, e, tag),
                "bt_sha1_verifier_commit")
+
+    def commit_gather(self, slot, segs, expected, tag):
+        """Queue the chunk made of segs, a list of (off, len) within the slot, in this order."""
+        e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
+        table = (Seg * max(len(segs), 1))(*[Seg(off, length, 0) for off, length in segs])
+        _check(lib.bt_sha1_verifier_commit_gather(self.h, slot, table, len(segs), e, tag),
+               "bt_sha1_verifier_commit_gather")
 
     def release(self, slot):
         _check(lib.bt_sha1_verifier_release(self.h, slot), "bt_sha1_verifier_release")
@@ -555,6 +600,12 @@ class Verifier:
         s = VerifierStats()
         _check(lib.bt_sha1_verifier_get_stats(self.h, ctypes.byref(s)), "bt_sha1_verifier_get_stats")
         return {k: getattr(s, k) for k, _ in VerifierStats._fields_}
+
+    def gather_stats(self):
+        """bt_sha1_verifier_get_gather_stats as a dict."""
+        s = VerifierGatherStats()
+        _check(lib.bt_sha1_verifier_get_gather_stats(self.h, ctypes.byref(s)), "bt_sha1_verifier_get_gather_stats")
+        return {k: getattr(s, k) for k, _ in VerifierGatherStats._fields_}
 
     def close(self):
         if self.h:

@@ -429,6 +429,39 @@ int bt_sha1_ragged_verify_dev(const void *d_base, const uint64_t *d_offsets, con
   return 0;
 }
 
+static int gather_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                      const uint32_t *d_seg_count, uint64_t n, uint8_t *d_digests, const uint8_t *d_expected,
+                      uint8_t *d_ok, bool verify, void *stream) {
+  if (n == 0) return 0;
+  if (!d_base || !d_segs || !d_seg_first || !d_seg_count || (verify ? !d_expected || !d_ok : !d_digests)) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (n > BTSHA1_GATHER_MAX) {  // one message per lane of 64-thread workgroups
+    set_err("gather: %llu messages exceed the grid limit of %llu per launch", (unsigned long long)n,
+            (unsigned long long)BTSHA1_GATHER_MAX);
+    return -1;
+  }
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  DevCtx *c = ctx_for(dev);
+  if (!c) return -1;
+  hipStream_t st = pick_stream(stream);
+  BT_CK(btsha1_launch_gather(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, d_expected, d_ok, st));
+  return 0;
+}
+
+int bt_sha1_gather_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                       const uint32_t *d_seg_count, uint64_t n, uint8_t *d_digests, void *stream) {
+  return gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, nullptr, nullptr, false, stream);
+}
+
+int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                              const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
+                              uint8_t *d_digests, void *stream) {
+  return gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, d_expected, d_ok, true, stream);
+}
+
 int bt_sha1_states_init_dev(uint32_t *d_states, uint64_t n, void *stream) {
   if (n == 0) return 0;
   if (!d_states) {

@@ -19,6 +19,13 @@
 // verifier launches; any other batch is copied the same way and hashed by ONE
 // btsha1_launch_ragged_verify over (i * pitch, length i), both read by the
 // kernel in place from per-batch pinned arrays, released slots with length 0.
+//
+// A gather verifier (bt_sha1_verifier_create_gather) holds DATAGRAMS in its
+// slots: packets stay where recvfrom put them, header and payload, in arrival
+// order, and commit_gather lists the payloads in sequence order.  Every batch
+// is one copy of its slots as they are and ONE btsha1_launch_gather over the
+// batch's pinned segment table; slot i's segments stand at i * max_segs, so
+// commits in any order need no compaction.  Released slots have count 0.
 #include "bt_columns.h"
 #include "bt_runtime.h"
 
@@ -41,6 +48,11 @@ struct VBatch {
   // committed length (0: released, or not handed out)
   uint64_t *h_off = nullptr;
   uint32_t *h_len = nullptr;
+  // gather verifiers only (pinned, read by the kernel in place): slot i's segments at h_segs[i * max_segs ..]
+  // with offsets from d_in, h_first[i] = i * max_segs, and their count (0: released, or not handed out)
+  bt_sha1_seg *h_segs = nullptr;
+  uint64_t *h_first = nullptr;
+  uint32_t *h_count = nullptr;
   uint8_t *d_in = nullptr;
   std::vector<uint64_t> tags;
   std::vector<uint8_t> state;  // per slot: 0 free, 1 handed out, 2 committed, 3 released
@@ -53,7 +65,10 @@ struct bt_sha1_verifier {
   uint32_t chunk_len = 0, batch = 0;  // chunk_len: every chunk's length, or a ragged verifier's max_chunk_len
   uint32_t pitch = 0;                 // slot i of a batch at i * pitch: chunk_len, rounded up to 16 bytes when ragged
   bool ragged = false;
+  bool gather = false;    // chunk_len is then the slot length
+  uint32_t max_segs = 0;  // gather: segments per chunk at most
   bt_sha1_verifier_stats st = {};
+  bt_sha1_verifier_gather_stats gs = {};
   std::vector<VBatch> b;
   uint32_t fill = 0;             // batch handing out slots
   std::deque<uint32_t> order;    // batches in flight, oldest first
@@ -122,6 +137,17 @@ int v_launch(bt_sha1_verifier *v, uint32_t idx) {
     return 0;
   }
   ++v->st.batches;
+  if (v->gather) {  // the slots as they are, one launch over the segment table
+    const size_t bytes = (size_t)b.reserved * v->pitch;
+    ++v->gs.gather_batches;
+    v->gs.copied_bytes += bytes;
+    BT_CK(hipMemcpyAsync(b.d_in, b.h_in, bytes, hipMemcpyHostToDevice, b.s));
+    BT_CK(btsha1_launch_gather(b.d_in, b.h_segs, b.h_first, b.h_count, b.reserved, b.h_dig, b.h_exp, b.h_ok, b.s));
+    BT_CK(hipEventRecord(b.ev, b.s));
+    b.inflight = true;
+    v->order.push_back(idx);
+    return 0;
+  }
   if (v_needs_ragged(v, b)) {  // one copy, one launch, no column split
     ++v->st.ragged_batches;
     BT_CK(hipMemcpyAsync(b.d_in, b.h_in, (size_t)b.reserved * v->pitch, hipMemcpyHostToDevice, b.s));
@@ -198,7 +224,12 @@ int v_locate(bt_sha1_verifier *v, const uint8_t *slot, uint32_t *bi, uint32_t *s
 // The chunk length a commit or a submit brings: exactly chunk_len, or for a
 // ragged verifier anything from 1 to max_chunk_len.
 int v_check_len(const bt_sha1_verifier *v, uint32_t len) {
-  if (v->ragged) {
+  if (v->gather) {
+    if (len == 0 || len > v->chunk_len) {
+      set_err("verifier: chunk of %u bytes, gather verifier's slots take 1 .. %u", len, v->chunk_len);
+      return -1;
+    }
+  } else if (v->ragged) {
     if (len == 0 || len > v->chunk_len) {
       set_err("verifier: chunk of %u bytes, ragged verifier takes 1 .. %u", len, v->chunk_len);
       return -1;
@@ -210,7 +241,9 @@ int v_check_len(const bt_sha1_verifier *v, uint32_t len) {
   return 0;
 }
 
-bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint32_t nstreams, bool ragged) {
+bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint32_t nstreams, bool ragged,
+                           uint32_t max_segs = 0) {
+  const bool gather = max_segs != 0;
   DevCtx *c = ctx_for(device);
   if (!c) return nullptr;
   KeepDevice keep_dev;
@@ -229,8 +262,10 @@ bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint3
   auto *v = new bt_sha1_verifier;
   v->dev = device;
   v->chunk_len = chunk_len;
-  v->pitch = ragged ? (chunk_len + 15u) & ~15u : chunk_len;
+  v->pitch = ragged || gather ? (chunk_len + 15u) & ~15u : chunk_len;
   v->ragged = ragged;
+  v->gather = gather;
+  v->max_segs = max_segs;
   v->batch = batch;
   v->b.resize(std::max<uint32_t>(nstreams, 2));
   const size_t bytes = (size_t)batch * v->pitch;
@@ -246,7 +281,12 @@ bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint3
         hipHostMalloc((void **)&b.h_dig, 20 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
         hipMalloc((void **)&b.d_in, bytes) != hipSuccess ||
         (ragged && (hipHostMalloc((void **)&b.h_off, 8 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
-                    hipHostMalloc((void **)&b.h_len, 4 * (size_t)batch, hipHostMallocDefault) != hipSuccess))) {
+                    hipHostMalloc((void **)&b.h_len, 4 * (size_t)batch, hipHostMallocDefault) != hipSuccess)) ||
+        (gather &&
+         (hipHostMalloc((void **)&b.h_segs, sizeof(bt_sha1_seg) * (size_t)batch * max_segs, hipHostMallocDefault) !=
+              hipSuccess ||
+          hipHostMalloc((void **)&b.h_first, 8 * (size_t)batch, hipHostMallocDefault) != hipSuccess ||
+          hipHostMalloc((void **)&b.h_count, 4 * (size_t)batch, hipHostMallocDefault) != hipSuccess))) {
       if (t_err.empty()) set_err("verifier: allocation failed");
       bt_sha1_verifier_destroy(v);
       return nullptr;
@@ -255,6 +295,10 @@ bt_sha1_verifier *v_create(int device, uint32_t chunk_len, uint32_t batch, uint3
     for (uint32_t i = 0; ragged && i < batch; ++i) {
       b.h_off[i] = (uint64_t)i * v->pitch;
       b.h_len[i] = 0;
+    }
+    for (uint32_t i = 0; gather && i < batch; ++i) {
+      b.h_first[i] = (uint64_t)i * max_segs;
+      b.h_count[i] = 0;
     }
   }
   return v;
@@ -281,6 +325,68 @@ bt_sha1_verifier *bt_sha1_verifier_create_ragged(int device, uint32_t max_chunk_
   return v_create(device, max_chunk_len, batch, nstreams, true);
 }
 
+bt_sha1_verifier *bt_sha1_verifier_create_gather(int device, uint32_t slot_len, uint32_t max_segs, uint32_t batch,
+                                                 uint32_t nstreams) {
+  if (slot_len == 0 || slot_len > (33u << 20) || max_segs == 0 || batch == 0 ||
+      (uint64_t)batch * max_segs * sizeof(bt_sha1_seg) > (256ull << 20)) {
+    set_err("verifier: slot_len must be in [1, 33 MiB], max_segs > 0, batch > 0 and batch x max_segs x 16 <= 256 MiB");
+    return nullptr;
+  }
+  return v_create(device, slot_len, batch, nstreams, false, max_segs);
+}
+
+int bt_sha1_verifier_commit_gather(bt_sha1_verifier *v, uint8_t *slot, const bt_sha1_seg *segs, uint32_t nseg,
+                                   const uint8_t expected[20], uint64_t tag) {
+  if (!v || !slot || !expected || (nseg && !segs)) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (!v->gather) {
+    set_err("verifier: commit_gather needs a verifier from bt_sha1_verifier_create_gather");
+    return -1;
+  }
+  if (nseg > v->max_segs) {
+    set_err("verifier: %u segments, gather verifier built for %u per chunk", nseg, v->max_segs);
+    return -1;
+  }
+  uint64_t payload = 0;
+  for (uint32_t k = 0; k < nseg; ++k) {
+    if (segs[k].off > v->chunk_len || segs[k].len > v->chunk_len - segs[k].off) {
+      set_err("verifier: segment %u (offset %llu, %u bytes) ends past the slot's %u bytes", k,
+              (unsigned long long)segs[k].off, segs[k].len, v->chunk_len);
+      return -1;
+    }
+    payload += segs[k].len;
+  }
+  KeepDevice keep_dev;
+  if (hipSetDevice(v->dev) != hipSuccess) return -1;
+  uint32_t bi, si;
+  if (v_locate(v, slot, &bi, &si)) return -1;
+  VBatch &b = v->b[bi];
+  memcpy(b.h_exp + 20 * (size_t)si, expected, 20);
+  bt_sha1_seg *t = b.h_segs + (size_t)si * v->max_segs;
+  for (uint32_t k = 0; k < nseg; ++k) t[k] = bt_sha1_seg{(uint64_t)si * v->pitch + segs[k].off, segs[k].len, 0};
+  b.h_count[si] = nseg;
+  ++v->gs.gather_chunks;
+  v->gs.segments += nseg;
+  v->gs.payload_bytes += payload;
+  ++v->st.chunks;
+  b.tags[si] = tag;
+  b.state[si] = 2;
+  ++b.settled;
+  ++v->queued;
+  return v_maybe_launch(v, bi);
+}
+
+int bt_sha1_verifier_get_gather_stats(bt_sha1_verifier *v, bt_sha1_verifier_gather_stats *out) {
+  if (!v || !out) {
+    set_err("null pointer");
+    return -1;
+  }
+  *out = v->gs;
+  return 0;
+}
+
 void bt_sha1_verifier_destroy(bt_sha1_verifier *v) {
   if (!v) return;
   KeepDevice keep_dev;
@@ -300,6 +406,9 @@ void bt_sha1_verifier_destroy(bt_sha1_verifier *v) {
     if (b.h_dig) (void)hipHostFree(b.h_dig);
     if (b.h_off) (void)hipHostFree(b.h_off);
     if (b.h_len) (void)hipHostFree(b.h_len);
+    if (b.h_segs) (void)hipHostFree(b.h_segs);
+    if (b.h_first) (void)hipHostFree(b.h_first);
+    if (b.h_count) (void)hipHostFree(b.h_count);
     if (b.d_in) (void)hipFree(b.d_in);
   }
   delete v;
@@ -331,8 +440,15 @@ int bt_sha1_verifier_commit(bt_sha1_verifier *v, uint8_t *slot, uint32_t len, co
   VBatch &b = v->b[bi];
   memcpy(b.h_exp + 20 * (size_t)si, expected, 20);
   if (v->ragged) b.h_len[si] = len;
+  if (v->gather) {  // the one-segment message (0, len)
+    b.h_segs[(size_t)si * v->max_segs] = bt_sha1_seg{(uint64_t)si * v->pitch, len, 0};
+    b.h_count[si] = 1;
+    ++v->gs.gather_chunks;
+    ++v->gs.segments;
+    v->gs.payload_bytes += len;
+  }
   ++v->st.chunks;
-  if (len < v->chunk_len) ++v->st.short_chunks;
+  if (!v->gather && len < v->chunk_len) ++v->st.short_chunks;
   b.tags[si] = tag;
   b.state[si] = 2;
   ++b.settled;
@@ -352,6 +468,7 @@ int bt_sha1_verifier_release(bt_sha1_verifier *v, uint8_t *slot) {
   VBatch &b = v->b[bi];
   memset(b.h_exp + 20 * (size_t)si, 0, 20);
   if (v->ragged) b.h_len[si] = 0;  // hashed as an empty message; no verdict (v_harvest)
+  if (v->gather) b.h_count[si] = 0;
   ++v->st.released;
   b.state[si] = 3;
   ++b.settled;

@@ -1,0 +1,262 @@
+// sha1_gather_walk.h -- the block walk of the scatter-gather SHA-1 kernels
+// (k_sha1_gather, sha1_kernels.hip): a cursor over a message's segment list
+// -> one 64-byte block as 16 big-endian words (sha.c:186-189).
+//
+// Plain C++ that compiles for the device and for the host: the CPU check
+// (tests/native/gather_walk_check.cpp) runs this very text under
+// AddressSanitizer with every segment in an allocation of its own, because the
+// walk's contract is about addresses: NO BYTE OUTSIDE THE LISTED SEGMENTS IS
+// READ (the caller may be writing elsewhere in the slot; a segment may end an
+// allocation).  Every load below lies inside one segment of the message; where
+// a load has nothing to fetch its address is clamped to bytes of a segment
+// that the block reads anyway, never branched around (absorb_ring's reason:
+// a load inside a branch costs the prefetch its overlap).
+//
+// Two ways to a block:
+//   regular  the block lies in the current segment A, or in A's last a bytes
+//            (1 <= a < 64) and the head of the next segment B, both at least 16
+//            bytes long.  Four unaligned 16-byte loads at A + 16*i or
+//            B + 16*i - a; the one quad that straddles the cut is merged from
+//            two 16-byte windows, A's last 16 bytes (loaded in that quad's
+//            place) and B's first 16 (a fifth load), with a funnel shift.  No
+//            branch: the cursor step, the five addresses and the merge are
+//            selects.  This is every block
+//            of a chunk received as datagrams but its last.
+//   bytes    anything else (segments shorter than 16 bytes, three or more
+//            segments in a block, empty segments, the message's tail): one
+//            byte load per byte, stepping over segments as they run out.
+// gather_walk() runs a message through both, keeping one regular block in
+// flight ahead of the block being consumed.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define BT_GATHER_HD __host__ __device__ __forceinline__
+#else
+#define BT_GATHER_HD inline
+#endif
+
+namespace btsha1 {
+
+struct GatherSeg {  // bt_sha1_seg (include/bt_sha1.h)
+  uint64_t off;
+  uint32_t len;
+  uint32_t reserved;
+};
+static_assert(sizeof(GatherSeg) == 16, "segment layout");
+
+struct GatherQuad {
+  uint32_t v[4];
+};
+
+// Where the message stands: segment ja ("A") with ra of its la bytes unread
+// at pa, and a copy of segment ja + 1 ("B"; lb == 0 when there is none), read
+// one segment ahead so that stepping into B waits for no table load.
+struct GatherCursor {
+  const uint8_t *base;
+  const GatherSeg *segs;  // the message's first segment
+  uint32_t nseg, ja;
+  const uint8_t *pa;
+  uint32_t ra, la;
+  uint64_t boff;
+  uint32_t lb;
+  uint64_t total;  // bytes taken so far; the message's length once it is exhausted
+};
+
+// The addresses of one regular block (all inside A or B) and how to merge.
+struct GatherPlan {
+  const uint8_t *q[4];
+  const uint8_t *wb;
+  uint32_t sq, c;  // quad sq (4: none) = A's last c bytes, then B's first 16 - c
+};
+
+struct GatherSlot {
+  GatherQuad q[4], wb;
+  uint32_t sq, c;
+};
+
+BT_GATHER_HD GatherSeg gather_seg(const GatherSeg *p) {
+  GatherSeg s;
+  __builtin_memcpy(&s, p, sizeof s);
+  return s;
+}
+
+BT_GATHER_HD void gather_load_b(GatherCursor &c) {
+  c.boff = 0;
+  c.lb = 0;
+  if (c.ja + 1 < c.nseg) {
+    const GatherSeg s = gather_seg(c.segs + c.ja + 1);
+    c.boff = s.off;
+    c.lb = s.len;
+  }
+}
+
+BT_GATHER_HD void gather_begin(GatherCursor &c, const uint8_t *base, const GatherSeg *segs, uint32_t nseg) {
+  c.base = base;
+  c.segs = segs;
+  c.nseg = nseg;
+  c.ja = 0;
+  c.pa = base;
+  c.ra = c.la = 0;
+  c.total = 0;
+  if (nseg) {
+    const GatherSeg s = gather_seg(segs);
+    c.pa = base + s.off;
+    c.ra = c.la = s.len;
+  }
+  gather_load_b(c);
+}
+
+BT_GATHER_HD bool gather_regular(const GatherCursor &c) {
+  return c.ra >= 64u || (c.ra >= 1u && c.la >= 16u && c.lb >= 16u && c.lb >= 64u - c.ra);
+}
+
+// Needs gather_regular(c).  The addresses of the next block, then the cursor
+// moves past it; its one table load (the new B, or B again) is issued here,
+// before the block's own loads, so that waiting for it never waits for them.
+BT_GATHER_HD void gather_plan(GatherCursor &c, GatherPlan &p) {
+  const uint32_t a = c.ra < 64u ? c.ra : 64u;
+  const bool cut = a < 64u;
+  const uint8_t *pb = cut ? c.base + c.boff : c.pa;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) {
+    const uint32_t lo = 16u * i;
+    const uint8_t *in_a = c.pa + lo, *in_b = pb + lo - a, *win_a = c.pa + a - 16u;
+    p.q[i] = lo + 16u <= a ? in_a : (lo >= a ? in_b : win_a);
+  }
+  p.wb = pb;
+  p.c = a & 15u;
+  p.sq = cut && p.c ? a >> 4 : 4u;
+  // Step: past 64 bytes of A; into B when the block cut into it, or when A is
+  // used up exactly.
+  const uint32_t into_b = cut ? 64u - a : 0u;
+  const bool step = cut || c.ra == 64u;
+  c.total += 64u;
+  c.pa = step ? c.base + c.boff + into_b : c.pa + 64u;
+  c.ra = step ? c.lb - into_b : c.ra - 64u;
+  c.la = step ? c.lb : c.la;
+  c.ja += step ? 1u : 0u;
+  // B again, or the new B after a step: one unconditional descriptor load per
+  // block.  Guarding it with `if (step)` was tried: the wave then waits for the
+  // descriptor inside the branch (s_waitcnt vmcnt(0) behind it in the listing),
+  // one memory round trip per block in which any lane steps -- 94 % of them.
+  uint32_t jb = c.ja + 1u;
+  const bool has_b = jb < c.nseg;
+  jb = has_b ? jb : c.nseg - 1u;
+  const GatherSeg s = gather_seg(c.segs + jb);
+  c.boff = s.off;
+  c.lb = has_b ? s.len : 0u;
+}
+
+BT_GATHER_HD void gather_fetch(GatherSlot &s, const GatherPlan &p) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) __builtin_memcpy(&s.q[i], p.q[i], 16);
+  __builtin_memcpy(&s.wb, p.wb, 16);
+  s.sq = p.sq;
+  s.c = p.c;
+}
+
+// c ? a : b with both sides evaluated first.  A `?:` whose arms read two
+// elements of an array is compiled into ONE read at a selected index, which
+// puts the array into scratch memory; values passed through here stay in
+// registers.
+BT_GATHER_HD uint32_t gather_sel(bool c, uint32_t a, uint32_t b) { return c ? a : b; }
+
+// The fetched block as 16 big-endian words.  The straddling quad is bytes
+// [16 - c, 32 - c) of (A's last 16 bytes : B's first 16): a word shift of
+// (16 - c) / 4 in two select stages, then a funnel shift by the odd bytes.
+BT_GATHER_HD void gather_words(uint32_t (&w)[16], const GatherSlot &s) {
+  uint32_t x[8];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    uint32_t v = s.q[0].v[k];
+    v = gather_sel(s.sq == 1u, s.q[1].v[k], v);
+    v = gather_sel(s.sq == 2u, s.q[2].v[k], v);
+    v = gather_sel(s.sq == 3u, s.q[3].v[k], v);
+    x[k] = v;
+    x[4 + k] = s.wb.v[k];
+  }
+  const uint32_t sh = 16u - s.c, bits = (sh & 3u) * 8u;
+  uint32_t y[6], z[5], m[4];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) y[k] = gather_sel(sh & 8u, x[k + 2], x[k]);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) z[k] = gather_sel(sh & 4u, y[k + 1], y[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) m[k] = (z[k] >> bits) | ((z[k + 1] << 1) << (31u - bits));
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[4 * i + k] = __builtin_bswap32(gather_sel(s.sq == (uint32_t)i, m[k], s.q[i].v[k]));
+}
+
+// One block by bytes, from any cursor: w = the next up to 64 bytes as
+// big-endian words, zero past them; returns how many there were (fewer than
+// 64 only where the message ends).  Leaves the cursor as gather_begin would.
+BT_GATHER_HD uint32_t gather_bytes(GatherCursor &c, uint32_t (&w)[16]) {
+  uint32_t got = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    uint32_t v = 0;
+#pragma nounroll
+    for (uint32_t b = 0; b < 4; ++b) {
+      while (c.ra == 0 && c.ja + 1 < c.nseg) {
+        const GatherSeg s = gather_seg(c.segs + ++c.ja);
+        c.pa = c.base + s.off;
+        c.ra = c.la = s.len;
+      }
+      if (c.ra) {
+        v |= (uint32_t)*c.pa++ << (24u - 8u * b);
+        --c.ra;
+        ++got;
+      }
+    }
+    w[k] = v;
+  }
+  c.total += got;
+  gather_load_b(c);
+  return got;
+}
+
+// The whole message: sink.block(w) for each whole block, in order; then w
+// holds the r = length % 64 trailing bytes (zero past them) and r is returned,
+// with c.total the message's length.  sink.fence() stands between a block's
+// loads being issued and the previous block being consumed (the device pins
+// the order there; the host does nothing).
+template <class Sink>
+BT_GATHER_HD uint32_t gather_walk(GatherCursor &c, uint32_t (&w)[16], Sink &sink) {
+  for (;;) {
+    if (gather_regular(c)) {
+      GatherPlan p;
+      // Two slots that swap roles by position in the loop, not by a copy: a
+      // copy of the slot just fetched would wait for its loads on the spot.
+      GatherSlot s0, s1;
+      gather_plan(c, p);
+      gather_fetch(s0, p);
+      while (gather_regular(c)) {
+        gather_plan(c, p);
+        gather_fetch(s1, p);
+        sink.fence();
+        gather_words(w, s0);
+        sink.block(w);
+        if (!gather_regular(c)) {
+          s0 = s1;  // long arrived: a block was consumed since its loads
+          break;
+        }
+        gather_plan(c, p);
+        gather_fetch(s0, p);
+        sink.fence();
+        gather_words(w, s1);
+        sink.block(w);
+      }
+      gather_words(w, s0);
+      sink.block(w);
+      continue;
+    }
+    const uint32_t got = gather_bytes(c, w);
+    if (got < 64u) return got;
+    sink.block(w);
+  }
+}
+
+}  // namespace btsha1

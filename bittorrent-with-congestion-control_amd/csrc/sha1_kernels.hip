@@ -31,6 +31,9 @@
 //                   offsets past 4 GiB per wave), one message per lane.
 //   k_sha1_lat_ragged_verify / k_sha1_ragged_verify  the two above with the
 //                   fused compare (a short last chunk, util.c:311-313).
+//   k_sha1_gather / k_sha1_gather_verify  messages given as lists of segments
+//                   (a chunk hashed where its datagrams landed), one message
+//                   per lane; the segment walk is sha1_gather_walk.h.
 //   k_fill_synthetic  frozen counter-based generator (bench/test data in HBM).
 //   k_lookup_build / k_lookup_query  digest -> first index table in HBM
 //                   (get_chunk_id / find_chunk, util.c:3-39).
@@ -38,6 +41,7 @@
 #include <stdint.h>
 
 #include "sha1_device.h"
+#include "sha1_gather_walk.h"
 #include "sha1_launch.h"
 
 namespace btsha1 {
@@ -1447,6 +1451,59 @@ __global__ __launch_bounds__(kBlock) void k_sha1_ragged_verify(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------
+// Scatter-gather: message i is the concatenation, in list order, of the
+// seg_count[i] segments segs[seg_first[i] ..], each base[off .. off + len) --
+// a chunk hashed where its datagrams landed (payloads of 1484 bytes behind
+// 16-byte headers, in arrival order), never assembled (util.c:275).  One
+// message per lane like k_sha1_ragged; the walk from segments to blocks is
+// sha1_gather_walk.h, which reads no byte outside the listed segments and
+// keeps one block in flight ahead of the one being compressed.  The length
+// that goes into the padding is the 64-bit sum of the segment lengths.
+// ---------------------------------------------------------------------------
+struct GatherCompress {
+  State &st;
+  __device__ __forceinline__ void fence() { __builtin_amdgcn_sched_barrier(0); }
+  __device__ __forceinline__ void block(uint32_t (&w)[16]) { compress(st, w); }
+};
+
+template <bool VERIFY>
+__device__ __forceinline__ void gather_body(const uint8_t *__restrict__ base, const GatherSeg *__restrict__ segs,
+                                            const uint64_t *__restrict__ seg_first,
+                                            const uint32_t *__restrict__ seg_count, uint64_t n,
+                                            uint8_t *__restrict__ digests, const uint8_t *__restrict__ expected,
+                                            uint8_t *__restrict__ ok) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  GatherCursor c;
+  gather_begin(c, base, segs + seg_first[i], seg_count[i]);
+  State st;
+  st.init();
+  GatherCompress sink{st};
+  uint32_t w[16];
+  const uint32_t r = gather_walk(c, w, sink);
+  finish(st, w, r, c.total);
+  store_digest_bytes<VERIFY>(st, i, digests, expected, ok);
+}
+
+__global__ __launch_bounds__(kBlock) void k_sha1_gather(const uint8_t *__restrict__ base,
+                                                        const GatherSeg *__restrict__ segs,
+                                                        const uint64_t *__restrict__ seg_first,
+                                                        const uint32_t *__restrict__ seg_count, uint64_t n,
+                                                        uint8_t *__restrict__ digests) {
+  gather_body<false>(base, segs, seg_first, seg_count, n, digests, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void k_sha1_gather_verify(const uint8_t *__restrict__ base,
+                                                               const GatherSeg *__restrict__ segs,
+                                                               const uint64_t *__restrict__ seg_first,
+                                                               const uint32_t *__restrict__ seg_count, uint64_t n,
+                                                               uint8_t *__restrict__ digests,
+                                                               const uint8_t *__restrict__ expected,
+                                                               uint8_t *__restrict__ ok) {
+  gather_body<true>(base, segs, seg_first, seg_count, n, digests, expected, ok);
+}
+
+// ---------------------------------------------------------------------------
 // Frozen synthetic generator: word g of the stream = splitmix64(seed + g),
 // stored little-endian (mirrored by oracle/sha1_oracle.c:or_fill_synthetic).
 // ---------------------------------------------------------------------------
@@ -1816,6 +1873,24 @@ hipError_t btsha1_launch_ragged_verify(const void *d_base, const uint64_t *d_off
   const uint64_t grid = (n + wg - 1) / wg;
   hipLaunchKernelGGL(k_sha1_ragged_verify, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)d_base, d_off, d_len,
                      pitch, fixed_len, n, d_dig, d_exp, d_ok);
+  return hipGetLastError();
+}
+
+// One message per lane at every n (no chain or loader / round-wave form walks
+// segments yet); the workgroup width as btsha1_launch_ragged's last form.
+hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64_t *seg_first,
+                                const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp, uint8_t *ok,
+                                hipStream_t s) {
+  if (!base || !segs || !seg_first || !seg_count || (ok && !exp) || n > BTSHA1_GATHER_MAX) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const uint32_t wg = chain_workgroup(n);
+  const uint64_t grid = (n + wg - 1) / wg;
+  if (ok)
+    hipLaunchKernelGGL(k_sha1_gather_verify, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_first, seg_count, n, dig, exp, ok);
+  else
+    hipLaunchKernelGGL(k_sha1_gather, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_first, seg_count, n, dig);
   return hipGetLastError();
 }
 

@@ -94,6 +94,20 @@ BTSHA1_HIDDEN hipError_t btsha1_launch_resume(const void *base, const uint64_t *
 BTSHA1_HIDDEN hipError_t btsha1_launch_ragged_verify(const void *d_base, const uint64_t *d_off, const uint32_t *d_len,
                                                      uint64_t pitch, uint32_t fixed_len, uint64_t n, uint8_t *d_dig,
                                                      const uint8_t *d_exp, uint8_t *d_ok, hipStream_t s);
+// Scatter-gather (k_sha1_gather / k_sha1_gather_verify, one message per lane):
+// message i is the concatenation, in list order, of the seg_count[i] segments
+// segs[seg_first[i] ..] (bt_sha1_seg: {u64 off; u32 len; u32 reserved}), each
+// base[off .. off + len), any alignment and length, in any address order,
+// shared or overlapping between messages; no byte outside them is read.  base
+// and the tables may be device or pinned host memory.  dig / exp / ok as
+// btsha1_launch_ragged_verify's (ok == NULL: digests only).
+// hipErrorInvalidValue and no launch for a null base, segs, seg_first or
+// seg_count, ok without exp, or n above BTSHA1_GATHER_MAX (the grid of its
+// 64-thread form).
+#define BTSHA1_GATHER_MAX (0x7fffffffull * 64ull)
+BTSHA1_HIDDEN hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64_t *seg_first,
+                                              const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp,
+                                              uint8_t *ok, hipStream_t s);
 // The single-message form (grid 1): offset, length and total are kernel
 // arguments, so a host object launches it with no device-side arrays.
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,

@@ -3,7 +3,7 @@
  * driven through the batched GPU verifier, end to end from host memory.
  *
  *   verify-stream [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every]
- *                 [-g verifiers] [-t] [-x] [-z] <data-file> <chunks-file>
+ *                 [-g verifiers] [-t] [-x] [-z | -G] <data-file> <chunks-file>
  *
  * For every chunk listed in <chunks-file> ("<id> <hex>" lines, as
  * parse_has_get_chunk_file reads them, util.c:90-93) the chunk's bytes are
@@ -26,6 +26,17 @@
  * verifiers then run side by side).  -w W: the first W rounds are untimed
  * (first touches of the data file's pages, slot pinning); -z with more than
  * one round always leaves round 0 untimed (it lands the data in the slots).
+ * -G ("datagram slots") is the honest form of -z: a recvfrom cannot land
+ * payloads contiguously, the 16-byte header arrives in front of each.  A
+ * chunk's slot holds its DATA datagrams whole (header: sequence number, payload
+ * length; then the payload) at slot + arrival_index * 1500, in a seeded
+ * pseudo-random arrival order (a permutation within windows of 8 datagrams)
+ * plus one duplicated datagram landed after its original -- one memcpy per
+ * datagram, standing for recvfrom into the slot.  Nothing is assembled: the
+ * commit reads the headers, lists the payloads by sequence number (the
+ * duplicate is not listed) and bt_sha1_verifier_commit_gather hashes them in
+ * place.  Rounds work as with -z; the timed rate is table build + H2D + gather
+ * hash + verdict, over hashed (payload) bytes.
  * The last line is a JSON summary with the host->verdict rate of the timed
  * rounds.
  *
@@ -49,6 +60,11 @@
 #include "chunk.h"
 
 #define PAYLOAD 1484 /* MAX_PAYLOAD_SIZE, common.h:30 */
+#define PACKET 1500  /* MAX_PACKET_SIZE, common.h:28 */
+#define HEADER (PACKET - PAYLOAD)
+#define MAX_DGRAMS ((BT_CHUNK_SIZE + PAYLOAD - 1) / PAYLOAD) /* 354 */
+#define GATHER_SLOT ((MAX_DGRAMS + 1) * PACKET)              /* and one duplicate */
+#define ARRIVAL_WINDOW 8
 
 /* util.c:316-318 for a failed chunk; tallies verdicts. */
 static void count(const bt_sha1_verdict *out, int m, long *good, long *bad) {
@@ -109,7 +125,7 @@ struct shared {
   const int *ids;
   const uint8_t *exp;
   const uint32_t *len; /* bytes of chunk k: BT_CHUNK_SIZE, less for the file's short last chunk */
-  int corrupt, zcopy, poll_every, rounds, warm;
+  int corrupt, zcopy, gather, poll_every, rounds, warm; /* zcopy: slots stay resident (-z and -G) */
   long ring;
   pthread_barrier_t *bar; /* -t: the lanes meet after the warm-up rounds */
   double *t0;             /* start of the timed rounds */
@@ -123,8 +139,8 @@ struct lane {
   long per_round;       /* commits per round */
   struct resident *res; /* -z: which chunk each of its pinned slots holds */
   long nres;
-  long good, bad, total, timed, late_fills, commits;
-  uint64_t timed_bytes;
+  long good, bad, total, timed, late_fills, commits, segments;
+  uint64_t timed_bytes, wire_bytes;
   int err;
   const struct shared *sh;
 };
@@ -139,6 +155,58 @@ static int drain_lane(struct lane *l, int wait) {
     return -1;
   }
   return 0;
+}
+
+static uint32_t next_rand(uint32_t *x) {
+  *x = *x * 1664525u + 1013904223u;
+  return *x >> 8;
+}
+
+static void land_one(uint8_t *at, uint32_t seq, const uint8_t *src, uint32_t clen, long flip) {
+  const uint32_t from = seq * PAYLOAD, len = clen - from < PAYLOAD ? clen - from : PAYLOAD;
+  memset(at, 0, HEADER);
+  memcpy(at, &seq, 4);
+  memcpy(at + 4, &len, 4);
+  memcpy(at + HEADER, src + from, len); /* recvfrom(slot + arrival * 1500) */
+  if (flip >= (long)from && flip < (long)(from + len)) at[HEADER + flip - from] ^= 0x5a;
+}
+
+/* -G: chunk k's datagrams into its slot in arrival order; `flip` is the payload
+ * byte -x corrupts (-1: none).  Returns the datagrams landed. */
+static uint32_t land_datagrams(uint8_t *slot, const uint8_t *src, uint32_t clen, int k, long flip) {
+  const uint32_t nd = (clen + PAYLOAD - 1) / PAYLOAD;
+  uint32_t rng = 0x9E3779B9u ^ (uint32_t)k, order[ARRIVAL_WINDOW];
+  for (uint32_t w = 0; w < nd; w += ARRIVAL_WINDOW) {
+    const uint32_t m = nd - w < ARRIVAL_WINDOW ? nd - w : ARRIVAL_WINDOW;
+    for (uint32_t j = 0; j < m; j++) order[j] = w + j;
+    for (uint32_t j = m; j > 1; j--) { /* Fisher-Yates */
+      const uint32_t t = next_rand(&rng) % j, o = order[j - 1];
+      order[j - 1] = order[t];
+      order[t] = o;
+    }
+    for (uint32_t j = 0; j < m; j++) land_one(slot + (size_t)(w + j) * PACKET, order[j], src, clen, flip);
+  }
+  land_one(slot + (size_t)nd * PACKET, next_rand(&rng) % nd, src, clen, flip); /* a retransmission */
+  return nd + 1;
+}
+
+/* -G: the segment list of a slot holding `landed` datagrams, by sequence
+ * number from their headers; a sequence number seen before is a duplicate and
+ * is not listed.  Returns the segments, 0 for a header that makes no sense. */
+static uint32_t list_segments(const uint8_t *slot, uint32_t landed, bt_sha1_seg *segs) {
+  uint32_t nseg = 0;
+  memset(segs, 0, sizeof *segs * MAX_DGRAMS);
+  for (uint32_t a = 0; a < landed; a++) {
+    uint32_t seq, len;
+    memcpy(&seq, slot + (size_t)a * PACKET, 4);
+    memcpy(&len, slot + (size_t)a * PACKET + 4, 4);
+    if (seq >= MAX_DGRAMS || len == 0 || len > PAYLOAD) return 0;
+    if (segs[seq].len) continue;
+    segs[seq].off = (uint64_t)a * PACKET + HEADER;
+    segs[seq].len = len;
+    nseg++;
+  }
+  return nseg;
 }
 
 /* The i-th receive of round r on lane l: a slot, the chunk's bytes landed in
@@ -180,7 +248,26 @@ static int receive_one(struct lane *l, int r, long i) {
       return -1;
     }
   }
-  if (!sh->zcopy || r == 0 || fill) {
+  if (sh->gather) {
+    const uint32_t clen = sh->len[k], landed = (clen + PAYLOAD - 1) / PAYLOAD + 1;
+    if (r == 0 || fill)
+      land_datagrams(slot, sh->img + (uint64_t)sh->ids[k] * BT_CHUNK_SIZE, clen, k,
+                     sh->corrupt && k % 7 == 3 ? (long)(k % clen) : -1);
+    bt_sha1_seg segs[MAX_DGRAMS];
+    const uint32_t nseg = list_segments(slot, landed, segs);
+    if (nseg != landed - 1) {
+      fprintf(stderr, "verify-stream -G: chunk %d: %u sequence numbers in %u datagrams\n", k, nseg, landed);
+      return -1;
+    }
+    if (bt_sha1_verifier_commit_gather(l->v, slot, segs, nseg, sh->exp + 20 * k, (uint64_t)k)) {
+      fprintf(stderr, "verify-stream: %s\n", bt_sha1_last_error());
+      return -1;
+    }
+    if (r >= sh->warm) {
+      l->segments += nseg;
+      l->wire_bytes += (uint64_t)landed * PACKET;
+    }
+  } else if (!sh->zcopy || r == 0 || fill) {
     const uint64_t off = (uint64_t)sh->ids[k] * BT_CHUNK_SIZE;
     const uint32_t clen = sh->len[k];
     for (uint32_t got = 0; got < clen; got += PAYLOAD) { /* save_data_packet, util.c:275 */
@@ -189,7 +276,7 @@ static int receive_one(struct lane *l, int r, long i) {
     }
     if (sh->corrupt && k % 7 == 3) slot[k % clen] ^= 0x5a;
   }
-  if (bt_sha1_verifier_commit(l->v, slot, sh->len[k], sh->exp + 20 * k, (uint64_t)k)) {
+  if (!sh->gather && bt_sha1_verifier_commit(l->v, slot, sh->len[k], sh->exp + 20 * k, (uint64_t)k)) {
     fprintf(stderr, "verify-stream: %s\n", bt_sha1_last_error());
     return -1;
   }
@@ -229,18 +316,20 @@ static void *lane_thread(void *arg) {
 }
 
 #define USAGE \
-  "usage: %s [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every] [-g verifiers] [-t] [-x] [-z] " \
+  "usage: %s [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every] [-g verifiers] [-t] [-x] [-z | -G] " \
   "<data-file> <chunks-file>\n"
 
 int main(int argc, char **argv) {
   int batch = 64, streams = 2, rounds = 1, corrupt = 0, zcopy = 0, poll_every = 1, G = 1, threads = 0, warm = 0, opt;
-  while ((opt = getopt(argc, argv, "b:s:r:w:p:g:txz")) != -1) {
+  int gather = 0;
+  while ((opt = getopt(argc, argv, "b:s:r:w:p:g:txzG")) != -1) {
     if (opt == 'b') batch = atoi(optarg);
     else if (opt == 's') streams = atoi(optarg);
     else if (opt == 'r') rounds = atoi(optarg);
     else if (opt == 'w') warm = atoi(optarg);
     else if (opt == 'x') corrupt = 1;
     else if (opt == 'z') zcopy = 1;
+    else if (opt == 'G') gather = 1;
     else if (opt == 't') threads = 1;
     else if (opt == 'p') poll_every = atoi(optarg) > 0 ? atoi(optarg) : 1;
     else if (opt == 'g') G = atoi(optarg);
@@ -249,11 +338,16 @@ int main(int argc, char **argv) {
       return 255;
     }
   }
+  if (gather && zcopy) {
+    fprintf(stderr, "verify-stream: -z and -G are two receive models, take one\n");
+    return 255;
+  }
+  const int resident = zcopy || gather; /* round 0 lands the data, later rounds re-commit it */
   if (argc - optind != 2 || G < 1 || G > 64 || rounds < 1 || warm < 0 || batch < 1) {
     fprintf(stderr, USAGE, argv[0]);
     return 255;
   }
-  if (zcopy && rounds > 1 && warm < 1) warm = 1; /* round 0 lands the data in the slots */
+  if (resident && rounds > 1 && warm < 1) warm = 1; /* round 0 lands the data in the slots */
   if (warm >= rounds) {
     fprintf(stderr, "verify-stream: -w %d leaves no timed round of %d\n", warm, rounds);
     return 255;
@@ -312,13 +406,15 @@ int main(int argc, char **argv) {
   }
   double t0 = 0;
   pthread_barrier_t bar;
-  struct shared sh = {img, ids, exp, clen, corrupt, zcopy, poll_every, rounds, warm,
+  struct shared sh = {img, ids, exp, clen, corrupt, resident, gather, poll_every, rounds, warm,
                       (long)batch * (streams < 2 ? 2 : streams), &bar, &t0};
   struct lane *L = calloc((size_t)G, sizeof *L);
   long per_round_max = 0;
   for (int g = 0; g < G; g++) {
     L[g].sh = &sh;
-    L[g].v = any_short ? bt_sha1_verifier_create_ragged(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams)
+    L[g].v = gather ? bt_sha1_verifier_create_gather(g % ndev, GATHER_SLOT, MAX_DGRAMS, (uint32_t)batch,
+                                                     (uint32_t)streams)
+             : any_short ? bt_sha1_verifier_create_ragged(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams)
                        : bt_sha1_verifier_create(g % ndev, BT_CHUNK_SIZE, (uint32_t)batch, (uint32_t)streams);
     if (!L[g].v) {
       fprintf(stderr, "verify-stream: %s\n", bt_sha1_last_error());
@@ -328,10 +424,10 @@ int main(int argc, char **argv) {
     for (int k = 0; k < n; k++)
       if (ids[k] % G == g) L[g].ks[L[g].nk++] = k;
     L[g].per_round = L[g].nk;
-    if (zcopy) {
+    if (resident) {
       if (L[g].nk == 0 || sh.ring % L[g].nk) {
-        fprintf(stderr, "verify-stream -z: batch*streams (%ld) must be a multiple of each verifier's chunk count "
-                        "(verifier %d: %d)\n", sh.ring, g, L[g].nk);
+        fprintf(stderr, "verify-stream %s: batch*streams (%ld) must be a multiple of each verifier's chunk count "
+                        "(verifier %d: %d)\n", gather ? "-G" : "-z", sh.ring, g, L[g].nk);
         return 255;
       }
       /* which chunk each pinned slot holds.  The verifier hands slots out in
@@ -373,8 +469,11 @@ int main(int argc, char **argv) {
   if (err) return 255;
   double dt = now() - t0;
   long good = 0, bad = 0, total = 0, timed = 0, late = 0;
-  uint64_t timed_bytes = 0;
+  uint64_t timed_bytes = 0, wire_bytes = 0;
+  long segments = 0;
   for (int g = 0; g < G; g++) {
+    segments += L[g].segments;
+    wire_bytes += L[g].wire_bytes;
     good += L[g].good;
     bad += L[g].bad;
     total += L[g].total;
@@ -389,9 +488,13 @@ int main(int argc, char **argv) {
   free(clen);
   printf("{\"chunks\": %ld, \"ok\": %ld, \"failed\": %ld, \"seconds\": %.6f, \"GiB_per_s\": %.4f, \"batch\": %d, "
          "\"streams\": %d, \"poll_every\": %d, \"verifiers\": %d, \"devices\": %d, \"receive_threads\": %d, "
-         "\"rounds\": %d, \"warmup_rounds\": %d, \"timed_chunks\": %ld, \"late_fills\": %ld, \"mode\": \"%s\"}\n",
+         "\"rounds\": %d, \"warmup_rounds\": %d, \"timed_chunks\": %ld, \"late_fills\": %ld, \"mode\": \"%s\"",
          total, good, bad, dt, (double)timed_bytes / dt / (1u << 30), batch, streams, poll_every, G,
          G < ndev ? G : ndev, threads ? G : 1, rounds, warm, timed, late,
-         zcopy ? "zero-copy slots" : "packetized memcpy (util.c:275)");
+         gather ? "datagram slots" : zcopy ? "zero-copy slots" : "packetized memcpy (util.c:275)");
+  if (gather) /* of the timed rounds, like the rate */
+    printf(", \"segments\": %ld, \"hashed_bytes\": %llu, \"wire_bytes\": %llu", segments,
+           (unsigned long long)timed_bytes, (unsigned long long)wire_bytes);
+  printf("}\n");
   return bad && !corrupt ? 1 : 0;
 }

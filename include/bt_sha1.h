@@ -159,6 +159,26 @@ int bt_sha1_ragged_dev(const void *d_base, const uint64_t *d_offsets, const uint
 int bt_sha1_ragged_verify_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
                               uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
                               uint8_t *d_digests /* may be NULL */, void *stream);
+/* Scatter-gather: message i is the concatenation, in list order, of the
+ * d_seg_count[i] segments d_segs[d_seg_first[i] ..], each d_base[off .. off +
+ * len) -- a chunk hashed where its DATA datagrams landed, never assembled
+ * (save_data_packet's memcpy, util.c:275).  Offsets and lengths take any
+ * value (length 0 included), segments any address order; messages may share
+ * or overlap segments; d_seg_count[i] == 0 is the empty message.  No byte
+ * outside the listed segments is read.  Data and tables may be device or
+ * pinned host memory.  n == 0 is no work; a null d_base / d_segs /
+ * d_seg_first / d_seg_count (/ d_digests, or d_expected / d_ok), or n above
+ * (2^31 - 1) * 64 (the grid), are -1 before any device call. */
+typedef struct {
+  uint64_t off;      /* from d_base (commit_gather: from the slot)            */
+  uint32_t len;
+  uint32_t reserved; /* not read                                              */
+} bt_sha1_seg;
+int bt_sha1_gather_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                       const uint32_t *d_seg_count, uint64_t n, uint8_t *d_digests, void *stream);
+int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                              const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected,
+                              uint8_t *d_ok, uint8_t *d_digests /* may be NULL */, void *stream);
 /* Resumable hashing of messages that are still arriving (a peer appends a
  * chunk's payloads in order, util.c:275, and hashes it only when complete,
  * util.c:311-313; SHA-1 resumes at every 64-byte boundary).  This is the
@@ -361,6 +381,35 @@ typedef struct {
   uint64_t released;        /* slots released                                 */
 } bt_sha1_verifier_stats;
 int bt_sha1_verifier_get_stats(bt_sha1_verifier *v, bt_sha1_verifier_stats *out);
+/* A verifier whose slots hold DATAGRAMS, not an assembled chunk: recvfrom /
+ * recvmmsg land whole packets (header and payload) anywhere in the slot, in
+ * arrival order, and commit_gather lists the payloads in sequence order; a
+ * retransmitted duplicate is simply not listed.  slot_len: 1 .. 33 MiB (354 x
+ * 1500 = 531,000 bytes for the reference's chunk; the pitch is slot_len
+ * rounded up to 16); max_segs >= 1: segments per chunk at most, with batch x
+ * max_segs x 16 bytes of pinned table at most 256 MiB.  NULL with a message
+ * for arguments out of range, before any device call.  Every batch is one
+ * copy of its slots as they are and ONE gather-verify launch (as
+ * bt_sha1_gather_verify_dev; tables, expected hashes, verdicts and digests in
+ * pinned memory in place; no column split).
+ * commit_gather: segs[k].off is relative to the slot.  nseg > max_segs, or a
+ * segment with off + len > slot_len, is -1 with a message: the slot stays
+ * outstanding, nothing is recorded, the verifier stays usable.  Refused on
+ * any other kind of verifier.
+ * bt_sha1_verifier_commit on such a verifier is the one-segment message
+ * (0, len), 1 <= len <= slot_len; everything else works unchanged. */
+bt_sha1_verifier *bt_sha1_verifier_create_gather(int device, uint32_t slot_len, uint32_t max_segs,
+                                                 uint32_t batch, uint32_t nstreams);
+int bt_sha1_verifier_commit_gather(bt_sha1_verifier *v, uint8_t *slot, const bt_sha1_seg *segs,
+                                   uint32_t nseg, const uint8_t expected[20], uint64_t tag);
+typedef struct {
+  uint64_t gather_batches;  /* batches launched through the gather kernel     */
+  uint64_t gather_chunks;   /* chunks committed to them                       */
+  uint64_t segments;        /* segments listed by those commits               */
+  uint64_t payload_bytes;   /* bytes hashed: the sum of the segment lengths   */
+  uint64_t copied_bytes;    /* bytes copied to the device: reserved x pitch   */
+} bt_sha1_verifier_gather_stats;
+int bt_sha1_verifier_get_gather_stats(bt_sha1_verifier *v, bt_sha1_verifier_gather_stats *out);
 
 /* ---- progressive receive (util.c:250-337 for in-order delivery) ---------- */
 /* The verifier above starts a chunk's serial chain when its last byte has

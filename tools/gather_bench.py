@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""tools/gather_bench.py -- what hashing a chunk where its datagrams landed costs.
+
+Device-resident: bt_sha1_gather_dev over n chunks of 512 KiB, each cut as 354
+DATA datagrams of 1500 bytes (16-byte header, 1484 bytes of payload, the last
+436), beside bt_sha1_ragged_dev over the same payload bytes laid out
+contiguously, at the same n.  HIP events around each launch, 2 warm-ups, the
+median of 5, and the ratio of the two.  The digests of both must be equal.
+Prints one JSON line per n (64, 4096, 32768 by default), with the time per
+64-byte block of one message (the serial chain every lane runs).  At the
+largest n that leaves bt_sha1_ragged_dev on its loader / round-wave form, the
+lane kernel k_sha1_ragged -- the kernel the gather kernel is modelled on -- is
+timed too, with the latency batch set to 0 for those launches.
+
+Host paths: verify-stream on ONE image (8 GiB by default) in a tmpfs file, in
+one session, one receive thread: -G (datagram slots: table build + H2D of the
+datagrams + gather hash + verdict), -z (payloads landed contiguously) and
+packetized (util.c:275's 1484-byte memcpys); -G and -z time 4 rounds over the
+resident slots after the landing round, packetized 2 rounds after 1 untimed.
+Rates are over hashed (payload) bytes.
+usage: gather_bench.py [--host-gib G] [--no-device] [N ...]
+"""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(HERE, "bittorrent-with-congestion-control_amd"))
+
+CHUNK, DGRAM, HEADER, PAYLOAD, LAST = 512 * 1024, 1500, 16, 1484, 436
+NDG = 354
+SLOT = NDG * DGRAM
+
+
+def host_paths(torch, bt, gib):
+    n = int(gib * 2**30) // CHUNK
+    dev = torch.empty(n * CHUNK, dtype=torch.uint8, device="cuda")
+    bt.fill_synthetic(dev.data_ptr(), n * CHUNK, 0, 0x0B175EED)
+    dig = torch.zeros(20 * n, dtype=torch.uint8, device="cuda")
+    bt.chunks_dev(dev.data_ptr(), n, CHUNK, CHUNK, dig.data_ptr())
+    torch.cuda.synchronize()
+    want = dig.cpu().numpy().tobytes()
+    shm = "/dev/shm"
+    if not os.path.isdir(shm) or shutil.disk_usage(shm).free < 2 * n * CHUNK:
+        shm = tempfile.gettempdir()
+    vs = os.path.join(HERE, "bittorrent-with-congestion-control_amd", "bin", "verify-stream")
+    with tempfile.TemporaryDirectory(dir=shm) as d:
+        img, lst = os.path.join(d, "img"), os.path.join(d, "img.chunks")
+        dev.cpu().numpy().tofile(img)
+        del dev
+        torch.cuda.empty_cache()
+        with open(lst, "w") as f:
+            for i in range(n):
+                f.write(f"{i} {want[20 * i:20 * i + 20].hex()}\n")
+        ring = ["-b", str(n // 2), "-s", "2"]  # resident modes: every chunk keeps a slot
+        rates = {}
+        for name, args in (("datagram_slots", ["-G", *ring, "-r", "5"]), ("zero_copy", ["-z", *ring, "-r", "5"]),
+                           ("packetized", ["-b", "1024", "-s", "2", "-r", "3", "-w", "1"])):
+            r = subprocess.run([vs, *args, img, lst], capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, (name, r.stdout[-1000:], r.stderr[-1000:])
+            js = json.loads(r.stdout.strip().splitlines()[-1])
+            assert js["failed"] == 0 and js["ok"] == js["chunks"], (name, js)
+            rates[name] = js["GiB_per_s"]
+            print(json.dumps({"host_path": name, "image_GiB": n * CHUNK / 2**30, **js}), flush=True)
+        print(json.dumps({"host_paths": rates,
+                          "datagram_over_zero_copy": round(rates["datagram_slots"] / rates["zero_copy"], 4),
+                          "expected_1484_over_1500": round(PAYLOAD / DGRAM, 4),
+                          "datagram_over_packetized": round(rates["datagram_slots"] / rates["packetized"], 3)}),
+              flush=True)
+
+
+def main():
+    import torch
+    import btsha1 as bt
+    ap = argparse.ArgumentParser()
+    ap.add_argument("sizes", nargs="*", type=int)
+    ap.add_argument("--host-gib", type=float, default=8.0)
+    ap.add_argument("--no-device", action="store_true")
+    a = ap.parse_args()
+    sizes = a.sizes or [64, 4096, 32768]
+    assert (NDG - 1) * PAYLOAD + LAST == CHUNK
+    if a.host_gib > 0:
+        host_paths(torch, bt, a.host_gib)
+    for n in [] if a.no_device else sizes:
+        wire = torch.empty(n * SLOT + 16, dtype=torch.uint8, device="cuda")
+        bt.fill_synthetic(wire.data_ptr(), (n * SLOT) & ~15, 0, 0x6A7E)
+        dg = wire[:n * SLOT].view(n, NDG, DGRAM)
+        flat = torch.empty(n * CHUNK, dtype=torch.uint8, device="cuda")
+        fv = flat.view(n, CHUNK)
+        fv[:, :(NDG - 1) * PAYLOAD] = dg[:, :NDG - 1, HEADER:].reshape(n, -1)
+        fv[:, (NDG - 1) * PAYLOAD:] = dg[:, NDG - 1, HEADER:HEADER + LAST]
+        seg = np.zeros((n, NDG, 2), dtype=np.uint64)
+        seg[:, :, 0] = (np.arange(n, dtype=np.uint64)[:, None] * SLOT + np.arange(NDG, dtype=np.uint64)[None, :] * DGRAM
+                        + HEADER)
+        seg[:, :, 1] = PAYLOAD
+        seg[:, NDG - 1, 1] = LAST
+        d_seg = torch.from_numpy(seg.view(np.uint8).reshape(-1)).cuda()
+        d_first = torch.arange(n, dtype=torch.int64, device="cuda") * NDG
+        d_count = torch.full((n,), NDG, dtype=torch.int32, device="cuda")
+        d_off = torch.arange(n, dtype=torch.int64, device="cuda") * CHUNK
+        d_len = torch.full((n,), CHUNK, dtype=torch.int32, device="cuda")
+        gd = torch.zeros(20 * n, dtype=torch.uint8, device="cuda")
+        rd = torch.zeros(20 * n, dtype=torch.uint8, device="cuda")
+
+        def gather():
+            bt.gather_dev(wire.data_ptr(), d_seg.data_ptr(), d_first.data_ptr(), d_count.data_ptr(), n, gd.data_ptr())
+
+        def ragged():
+            bt.ragged_dev(flat.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, rd.data_ptr())
+
+        def timed(fn):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b)
+
+        for _ in range(2):
+            gather()
+            ragged()
+        torch.cuda.synchronize()
+        assert torch.equal(gd, rd), n
+        tg, tr = [], []
+        for _ in range(5):
+            tg.append(timed(gather))
+            tr.append(timed(ragged))
+        mg, mr = statistics.median(tg), statistics.median(tr)
+        lanes = None
+        if n > 2 * torch.cuda.get_device_properties(0).multi_processor_count:
+            before = bt.set_latency_batch(0)  # ragged_dev then launches k_sha1_ragged
+            try:
+                for _ in range(2):
+                    ragged()
+                torch.cuda.synchronize()
+                assert torch.equal(gd, rd), n
+                lanes = statistics.median(timed(ragged) for _ in range(5))
+            finally:
+                bt.set_latency_batch(before)
+        blocks = CHUNK // 64 + 1
+        print(json.dumps({"n": n, "payload_bytes": n * CHUNK, "wire_bytes": n * SLOT,
+                          "gather_dev_median_ms": round(mg, 4), "ragged_dev_median_ms": round(mr, 4),
+                          "gather_over_ragged": round(mg / mr, 3),
+                          "k_sha1_ragged_median_ms": lanes and round(lanes, 4),
+                          "gather_over_k_sha1_ragged": lanes and round(mg / lanes, 3),
+                          "gather_GiB_s": round(n * CHUNK / 2**30 / (mg / 1e3), 2),
+                          "ragged_GiB_s": round(n * CHUNK / 2**30 / (mr / 1e3), 2),
+                          "gather_us_per_block": round(mg * 1e3 / blocks, 4),
+                          "ragged_us_per_block": round(mr * 1e3 / blocks, 4),
+                          "gather_dev_ms": [round(x, 4) for x in tg], "ragged_dev_ms": [round(x, 4) for x in tr],
+                          "source_id": bt.source_id()}), flush=True)
+        del wire, flat, dg, fv, d_seg
+
+
+if __name__ == "__main__":
+    main()
