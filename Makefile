@@ -114,6 +114,15 @@ $(WALKDIR)/gather_walk_check: tests/native/gather_walk_check.cpp $(CSRC)/sha1_ga
 	@mkdir -p $(WALKDIR)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
 
+# The same for the random access of the chain-form gather kernels (gather_seek,
+# gather_block_at, gather_tail_at), with the descriptor and pos tables cut off
+# at the listed prefix; tests/test_gather_seek_host.py builds and runs it too.
+SEEKDIR  := build_variants/gather_seek
+gather_seek_check: $(SEEKDIR)/gather_seek_check
+$(SEEKDIR)/gather_seek_check: tests/native/gather_seek_check.cpp $(CSRC)/sha1_gather_walk.h
+	@mkdir -p $(SEEKDIR)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
+
 # Barrier-accounting build: the latency / chain / ragged-latency kernels count
 # the s_barriers each wave executes and check them against the invariant they
 # rely on (sha1_kernels.hip, "Barrier accounting"); bt_sha1_debug_barrier_stats
@@ -171,4 +180,4 @@ clean:
 	rm -rf $(PKG)/build $(LIB) $(BIN)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check ubench sched_variants install clean
+.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check gather_seek_check ubench sched_variants install clean

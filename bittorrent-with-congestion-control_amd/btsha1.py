@@ -164,6 +164,12 @@ _sig("bt_sha1_intake_poll", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c
 _sig("bt_sha1_intake_drain", ctypes.c_int, _vp, ctypes.POINTER(Verdict), ctypes.c_int)
 _sig("bt_sha1_intake_pending", _i64, _vp)
 _sig("bt_sha1_intake_get_stats", ctypes.c_int, _vp, ctypes.POINTER(IntakeStats))
+# bt_sha1_gather_resume_dev / bt_sha1_intake_create_gather / _append / _commit_gather under their exported names
+_sig("bt_sha1_dgram_chain_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
+_sig("bt_sha1_dgram_slots_create", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+     ctypes.c_uint32)
+_sig("bt_sha1_dgram_slots_append", ctypes.c_int, _vp, _vp, _vp, ctypes.c_uint32)
+_sig("bt_sha1_dgram_slots_commit", ctypes.c_int, _vp, _vp, _vp, _u64)
 
 
 class ChunkEntry(ctypes.Structure):
@@ -321,6 +327,17 @@ def resume_dev(d_base, d_offsets, d_lens, d_totals, n, d_states, d_digests=None,
     != 0 finishes a message of that many bytes into d_digests / d_ok."""
     _check(lib.bt_sha1_resume_dev(d_base, d_offsets, d_lens, d_totals, n, d_states, d_digests, d_expected, d_ok,
                                   stream), "bt_sha1_resume_dev")
+
+
+def gather_resume_dev(d_base, d_segs, d_seg_pos, d_seg_first, d_seg_count, d_from, d_lens, d_totals, n, d_states,
+                      d_digests=None, d_expected=None, d_ok=None, stream=None):
+    """bt_sha1_gather_resume_dev: resume_dev over messages given as segment
+    lists (gather_dev's tables, the segments listed so far) with d_seg_pos
+    (uint64, parallel to d_segs: the message position of each segment's first
+    byte).  Message bytes [d_from[i] (uint64, a 64-byte multiple), d_from[i] +
+    d_lens[i] (uint32)) are hashed into d_states[5*i ..]; d_totals as resume_dev's."""
+    _check(lib.bt_sha1_dgram_chain_dev(d_base, d_segs, d_seg_pos, d_seg_first, d_seg_count, d_from, d_lens, d_totals,
+                                       n, d_states, d_digests, d_expected, d_ok, stream), "bt_sha1_gather_resume_dev")
 
 
 def fill_synthetic(d_buf, nbytes, first_word, seed, stream=None):
@@ -701,12 +718,21 @@ class Receiver:
 class Intake:
     """Progressive receive for many chunks at once (bt_sha1_intake_*): advance
     and commit only record what has arrived, and one kick (poll ends with one)
-    advances every due slot in a single launch."""
+    advances every due slot in a single launch.
 
-    def __init__(self, device=0, chunk_len=CHUNK, nslots=64, stride=0):
-        self.h = lib.bt_sha1_intake_create(device, chunk_len, nslots, stride)
+    gather=True (bt_sha1_intake_create_gather): a slot holds datagrams where
+    they landed, chunk_len is the slot's length and max_segs the most segments
+    a chunk may list; append / commit_gather take the place of advance /
+    commit, everything else is the same."""
+
+    def __init__(self, device=0, chunk_len=CHUNK, nslots=64, stride=0, gather=False, max_segs=0):
+        self.gather = bool(gather)
+        if self.gather:
+            self.h = lib.bt_sha1_dgram_slots_create(device, chunk_len, max_segs, nslots, stride)
+        else:
+            self.h = lib.bt_sha1_intake_create(device, chunk_len, nslots, stride)
         if not self.h:
-            raise BtSha1Error(f"bt_sha1_intake_create: {last_error()}")
+            raise BtSha1Error(f"bt_sha1_intake_create{'_gather' if self.gather else ''}: {last_error()}")
         self.chunk_len = chunk_len
         self.nslots = nslots
 
@@ -725,6 +751,47 @@ class Intake:
         e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
         _check(lib.bt_sha1_intake_commit(self.h, slot, self.chunk_len if length is None else length, e, tag),
                "bt_sha1_intake_commit")
+
+    def append(self, slot, segs):
+        """The next payload segments in sequence order, (off, len) pairs relative to the slot (recorded only)."""
+        arr = (Seg * max(len(segs), 1))()
+        for k, (off, length) in enumerate(segs):
+            arr[k].off, arr[k].len = off, length
+        _check(lib.bt_sha1_dgram_slots_append(self.h, slot, arr, len(segs)), "bt_sha1_intake_append")
+
+    def commit_gather(self, slot, expected, tag):
+        """The chunk is complete at the bytes listed."""
+        e = (ctypes.c_uint8 * 20).from_buffer_copy(bytes(expected))
+        _check(lib.bt_sha1_dgram_slots_commit(self.h, slot, e, tag), "bt_sha1_intake_commit_gather")
+
+    def receive_datagrams(self, chunk, order, expected, tag, payload=1484, header=16, each=None):
+        """One whole chunk as DATA datagrams (a `header`-byte header that
+        starts with the sequence number, then up to `payload` bytes) that
+        arrive in `order`, a list of sequence numbers in which every one occurs
+        and duplicates may: each lands where the last one ended, a duplicate
+        is never listed, and a payload is appended once the gap before it has
+        filled, together with those held back behind it.  each(slot), when
+        given, runs after every append (a test kicks there).  Then
+        commit_gather (no kick).  Returns the slot."""
+        data = bytes(chunk)
+        p = self.slot()
+        where, listed = {}, 0
+        for arrival, seq in enumerate(order):
+            part = data[seq * payload:(seq + 1) * payload]
+            at = arrival * (header + payload)
+            pkt = int(seq).to_bytes(4, "little") + bytes(header - 4) + part
+            ctypes.memmove(p + at, pkt, len(pkt))
+            where.setdefault(seq, (at + header, len(part)))
+            ready = []
+            while listed in where:
+                ready.append(where[listed])
+                listed += 1
+            if ready:
+                self.append(p, ready)
+                if each:
+                    each(p)
+        self.commit_gather(p, expected, tag)
+        return p
 
     def release(self, slot):
         _check(lib.bt_sha1_intake_release(self.h, slot), "bt_sha1_intake_release")

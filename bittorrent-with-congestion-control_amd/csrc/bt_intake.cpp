@@ -19,6 +19,7 @@
 // kernel.  No CPU hashing path.
 #include "bt_runtime.h"
 
+#include <cstddef>
 #include <deque>
 
 namespace btsha1 {
@@ -30,6 +31,18 @@ constexpr uint32_t kDefaultStride = 64u << 10;
 constexpr uint32_t kMaxChunk = 32u << 20;
 constexpr uint64_t kMaxPinned = 2ull << 30;  // what the host pipelines keep: 2 x 1 GiB lanes
 constexpr size_t kCtl = BTSHA1_TABLE_CTL;    // the receiver's control block (bt_receiver.cpp)
+constexpr uint32_t kMaxGatherSlot = 33u << 20;   // the gather verifier's slot bound (bt_verifier.cpp)
+constexpr uint64_t kMaxSegTables = 256ull << 20;  // descriptors + positions, 24 bytes per segment
+// A gather entry is a table entry with two of its pad words in use: the ring
+// of tables, published() and launch_finished() serve both kinds.
+static_assert(offsetof(BtSha1GatherEntry, slot) == offsetof(BtSha1TableEntry, slot) &&
+                  offsetof(BtSha1GatherEntry, from) == offsetof(BtSha1TableEntry, from) &&
+                  offsetof(BtSha1GatherEntry, len) == offsetof(BtSha1TableEntry, len) &&
+                  offsetof(BtSha1GatherEntry, total) == offsetof(BtSha1TableEntry, total) &&
+                  offsetof(BtSha1GatherEntry, seq) == offsetof(BtSha1TableEntry, seq) &&
+                  offsetof(BtSha1GatherEntry, nseg) == offsetof(BtSha1TableEntry, pad) &&
+                  sizeof(BtSha1GatherEntry) == sizeof(BtSha1TableEntry),
+              "gather entry layout");
 constexpr uint32_t kIV[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u, 0xc3d2e1f0u};  // sha.c:149-163
 
 enum : uint32_t { kFree = 0, kOut = 1, kCommitted = 2 };
@@ -46,6 +59,9 @@ struct ISlot {
   bool expected_held = false;       // commit found a launch in flight: `held` goes in at the finishing kick
   uint8_t held[20] = {};
   uint64_t tag = 0;
+  // Gather intake: segments listed so far (their bytes are `filled`) and the
+  // segment that holds message byte `hashed`, the next entry's seg_hint.
+  uint32_t nseg = 0, hint = 0;
   uint32_t *state() const { return reinterpret_cast<uint32_t *>(ctl); }
   uint8_t *expected() const { return ctl + 20; }
   uint8_t *digest() const { return ctl + 64; }
@@ -55,6 +71,7 @@ struct ISlot {
   void restart() {
     memcpy(state(), kIV, sizeof kIV);
     filled = hashed = len = 0;
+    nseg = hint = 0;
     due = finishing = expected_held = false;
   }
 };
@@ -75,6 +92,14 @@ struct Intake {
   size_t pitch = 0;
   uint8_t *h_data = nullptr, *h_ctl = nullptr;
   BtSha1TableEntry *h_tables = nullptr;  // kTables x kMaxSlots entries
+  // Gather intake (slots hold datagrams): per slot max_segs descriptors and
+  // their message positions, pinned; the kernel reads them in place.
+  bool gather = false;
+  uint32_t max_segs = 0;
+  bt_sha1_seg *h_segs = nullptr;
+  uint64_t *h_pos = nullptr;
+  bt_sha1_seg *segs(const ISlot &s) const { return h_segs + (size_t)(&s - slot) * max_segs; }
+  uint64_t *pos(const ISlot &s) const { return h_pos + (size_t)(&s - slot) * max_segs; }
   hipStream_t streams[kStreams] = {};
   ISlot slot[kMaxSlots];
   uint32_t order[kMaxSlots];  // committed slots, oldest first
@@ -194,10 +219,18 @@ int kick(Intake *r) {
       e.total = 0;
     }
     e.pad[0] = e.pad[1] = e.pad[2] = 0;
+    if (r->gather) {  // the same 32 bytes as a BtSha1GatherEntry: what is listed now, and where `from` lies
+      BtSha1GatherEntry &g = reinterpret_cast<BtSha1GatherEntry &>(e);
+      g.nseg = s.nseg;
+      g.seg_hint = s.hint;
+    }
   }
   hipStream_t &st = r->streams[r->head % kStreams];
   if (!st) BT_CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  const hipError_t err = btsha1_launch_resume_table(t, n, r->h_data, r->pitch, r->h_ctl, true, st);
+  const hipError_t err =
+      r->gather ? btsha1_launch_gather_resume_table(reinterpret_cast<const BtSha1GatherEntry *>(t), n, r->h_data,
+                                                    r->pitch, r->h_segs, r->h_pos, r->max_segs, r->h_ctl, true, st)
+                : btsha1_launch_resume_table(t, n, r->h_data, r->pitch, r->h_ctl, true, st);
   if (err != hipSuccess) {
     set_err("intake: resume kernel launch: %s", hipGetErrorString(err));
     return -1;
@@ -217,6 +250,10 @@ int kick(Intake *r) {
       r->stats.advanced_bytes += t[j].len;
     }
     s.hashed += t[j].len;
+    if (r->gather) {  // the segment that holds the next entry's first byte
+      const uint64_t *pos = r->pos(s);
+      while (s.hint + 1u < s.nseg && pos[s.hint + 1u] <= s.hashed) ++s.hint;
+    }
     set_due(r, s, false);
   }
   ++r->stats.launches;
@@ -283,6 +320,69 @@ ISlot *locate(Intake *r, const uint8_t *p) {
   return nullptr;
 }
 
+// The object behind both kinds, arguments already checked; max_segs != 0: a gather intake.
+bt_sha1_intake *make_intake(int device, uint32_t chunk_len, size_t pitch, uint32_t nslots, uint32_t stride,
+                            uint32_t max_segs) {
+  if (!ctx_for(device)) return nullptr;
+  KeepDevice keep_dev;
+  if (hipSetDevice(device) != hipSuccess) {
+    set_err("hipSetDevice(%d) failed", device);
+    return nullptr;
+  }
+  auto *r = new Intake;
+  r->dev = device;
+  r->chunk_len = chunk_len;
+  r->nslots = nslots;
+  r->stride = stride ? stride : kDefaultStride;
+  r->pitch = pitch;
+  r->gather = max_segs != 0;
+  r->max_segs = max_segs;
+  const size_t nsegs = (size_t)nslots * max_segs;
+  if (hipHostMalloc((void **)&r->h_data, r->pitch * nslots, hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void **)&r->h_ctl, kCtl * nslots, hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void **)&r->h_tables, sizeof(BtSha1TableEntry) * kTables * kMaxSlots, hipHostMallocDefault) !=
+          hipSuccess ||
+      (r->gather && (hipHostMalloc((void **)&r->h_segs, sizeof(bt_sha1_seg) * nsegs, hipHostMallocDefault) != hipSuccess ||
+                     hipHostMalloc((void **)&r->h_pos, sizeof(uint64_t) * nsegs, hipHostMallocDefault) != hipSuccess))) {
+    set_err("intake: allocation of %u pinned slots of %u bytes failed", nslots, chunk_len);
+    bt_sha1_intake_destroy(reinterpret_cast<bt_sha1_intake *>(r));
+    return nullptr;
+  }
+  memset(r->h_ctl, 0, kCtl * nslots);
+  for (uint32_t k = 0; k < nslots; ++k) {
+    r->slot[k].data = r->h_data + k * r->pitch;
+    r->slot[k].ctl = r->h_ctl + k * kCtl;
+    r->slot[k].restart();
+  }
+  return reinterpret_cast<bt_sha1_intake *>(r);
+}
+
+// What commit and commit_gather share: the slot is complete at len bytes.
+void commit_slot(Intake *r, ISlot *s, uint32_t len, const uint8_t expected[20], uint64_t tag) {
+  if (s->idle()) {
+    memcpy(s->expected(), expected, 20);
+  } else {  // line 0 of the control block belongs to the launch in flight
+    memcpy(s->held, expected, 20);
+    s->expected_held = true;
+  }
+  s->tag = tag;
+  s->filled = s->len = len;
+  s->status = kCommitted;
+  set_due(r, *s, true);
+  r->order[r->norder++] = (uint32_t)(s - r->slot);
+  ++r->queued;
+  ++r->stats.committed;
+}
+
+// advance / commit belong to assembled slots, append / commit_gather to datagram slots.
+int wrong_kind(const Intake *r, bool want_gather, const char *call) {
+  if (r->gather == want_gather) return 0;
+  set_err(want_gather ? "intake: %s needs a gather intake (bt_sha1_intake_create_gather)"
+                      : "intake: %s is refused on a gather intake: use append / commit_gather",
+          call);
+  return -1;
+}
+
 }  // namespace
 }  // namespace btsha1
 
@@ -304,33 +404,34 @@ bt_sha1_intake *bt_sha1_intake_create(int device, uint32_t chunk_len, uint32_t n
     set_err("intake: %u slots of %u bytes exceed the 2 GiB of pinned memory an intake may hold", nslots, chunk_len);
     return nullptr;
   }
-  if (!ctx_for(device)) return nullptr;
-  KeepDevice keep_dev;
-  if (hipSetDevice(device) != hipSuccess) {
-    set_err("hipSetDevice(%d) failed", device);
+  return make_intake(device, chunk_len, pitch, nslots, stride, 0);
+}
+
+bt_sha1_intake *bt_sha1_dgram_slots_create(int device, uint32_t slot_len, uint32_t max_segs, uint32_t nslots,
+                                           uint32_t stride) {
+  if (slot_len == 0 || slot_len > kMaxGatherSlot) {
+    set_err("gather intake: slot_len must be in [1, 33 MiB]");
     return nullptr;
   }
-  auto *r = new Intake;
-  r->dev = device;
-  r->chunk_len = chunk_len;
-  r->nslots = nslots;
-  r->stride = stride ? stride : kDefaultStride;
-  r->pitch = pitch;
-  if (hipHostMalloc((void **)&r->h_data, r->pitch * nslots, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void **)&r->h_ctl, kCtl * nslots, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void **)&r->h_tables, sizeof(BtSha1TableEntry) * kTables * kMaxSlots, hipHostMallocDefault) !=
-          hipSuccess) {
-    set_err("intake: allocation of %u pinned slots of %u bytes failed", nslots, chunk_len);
-    bt_sha1_intake_destroy(reinterpret_cast<bt_sha1_intake *>(r));
+  if (max_segs == 0) {
+    set_err("gather intake: max_segs must be at least 1");
     return nullptr;
   }
-  memset(r->h_ctl, 0, kCtl * nslots);
-  for (uint32_t k = 0; k < nslots; ++k) {
-    r->slot[k].data = r->h_data + k * r->pitch;
-    r->slot[k].ctl = r->h_ctl + k * kCtl;
-    r->slot[k].restart();
+  if (nslots == 0 || nslots > kMaxSlots) {
+    set_err("gather intake: nslots must be in [1, %u]", kMaxSlots);
+    return nullptr;
   }
-  return reinterpret_cast<bt_sha1_intake *>(r);
+  const size_t pitch = ((size_t)slot_len + 15) & ~(size_t)15;
+  if ((uint64_t)pitch * nslots > kMaxPinned) {
+    set_err("gather intake: %u slots of %u bytes exceed the 2 GiB of pinned memory an intake may hold", nslots,
+            slot_len);
+    return nullptr;
+  }
+  if ((uint64_t)nslots * max_segs * (sizeof(bt_sha1_seg) + sizeof(uint64_t)) > kMaxSegTables) {
+    set_err("gather intake: nslots x max_segs x 24 bytes of segment tables exceed 256 MiB");
+    return nullptr;
+  }
+  return make_intake(device, slot_len, pitch, nslots, stride, max_segs);
 }
 
 void bt_sha1_intake_destroy(bt_sha1_intake *rr) {
@@ -346,6 +447,8 @@ void bt_sha1_intake_destroy(bt_sha1_intake *rr) {
   if (r->h_data) (void)hipHostFree(r->h_data);
   if (r->h_ctl) (void)hipHostFree(r->h_ctl);
   if (r->h_tables) (void)hipHostFree(r->h_tables);
+  if (r->h_segs) (void)hipHostFree(r->h_segs);
+  if (r->h_pos) (void)hipHostFree(r->h_pos);
   delete r;
 }
 
@@ -375,6 +478,7 @@ int bt_sha1_intake_advance(bt_sha1_intake *rr, uint8_t *slot, uint32_t filled) {
     set_err("null pointer");
     return -1;
   }
+  if (wrong_kind(r, false, "advance")) return -1;
   ISlot *s = locate(r, slot);
   if (!s) return -1;
   if (filled < s->filled || filled > r->chunk_len) {
@@ -393,6 +497,7 @@ int bt_sha1_intake_commit(bt_sha1_intake *rr, uint8_t *slot, uint32_t len, const
     set_err("null pointer");
     return -1;
   }
+  if (wrong_kind(r, false, "commit")) return -1;
   ISlot *s = locate(r, slot);
   if (!s) return -1;
   if (len == 0 || len < s->hashed || len > r->chunk_len) {
@@ -400,19 +505,70 @@ int bt_sha1_intake_commit(bt_sha1_intake *rr, uint8_t *slot, uint32_t len, const
             r->chunk_len);
     return -1;
   }
-  if (s->idle()) {
-    memcpy(s->expected(), expected, 20);
-  } else {  // line 0 of the control block belongs to the launch in flight
-    memcpy(s->held, expected, 20);
-    s->expected_held = true;
+  commit_slot(r, s, len, expected, tag);
+  return 0;
+}
+
+int bt_sha1_dgram_slots_append(bt_sha1_intake *rr, uint8_t *slot, const bt_sha1_seg *segs, uint32_t nseg) {
+  Intake *r = impl(rr);
+  if (!r || !slot || (!segs && nseg)) {
+    set_err("null pointer");
+    return -1;
   }
-  s->tag = tag;
-  s->filled = s->len = len;
-  s->status = kCommitted;
-  set_due(r, *s, true);
-  r->order[r->norder++] = (uint32_t)(s - r->slot);
-  ++r->queued;
-  ++r->stats.committed;
+  if (wrong_kind(r, true, "append")) return -1;
+  ISlot *s = locate(r, slot);
+  if (!s) return -1;
+  // Everything is checked before anything is recorded.
+  if (nseg > r->max_segs - s->nseg) {
+    set_err("gather intake: %u more segments after %u exceed max_segs %u", nseg, s->nseg, r->max_segs);
+    return -1;
+  }
+  uint64_t total = s->filled;
+  for (uint32_t k = 0; k < nseg; ++k) {
+    if (segs[k].off > r->chunk_len || segs[k].len > r->chunk_len - segs[k].off) {
+      set_err("gather intake: segment %u (off %llu, len %u) reaches past slot_len %u", k,
+              (unsigned long long)segs[k].off, segs[k].len, r->chunk_len);
+      return -1;
+    }
+    total += segs[k].len;
+    if (total > kMaxChunk) {
+      set_err("gather intake: the listed segments exceed 32 MiB");
+      return -1;
+    }
+  }
+  // Descriptors and positions at and past the slot's nseg: a launch in flight
+  // on the slot reads only those below the nseg of its kick.
+  bt_sha1_seg *d = r->segs(*s) + s->nseg;
+  uint64_t *pos = r->pos(*s) + s->nseg;
+  uint64_t at = s->filled;
+  for (uint32_t k = 0; k < nseg; ++k) {
+    d[k].off = segs[k].off;
+    d[k].len = segs[k].len;
+    d[k].reserved = 0;
+    pos[k] = at;
+    at += segs[k].len;
+  }
+  s->nseg += nseg;
+  s->filled = (uint32_t)total;
+  const uint32_t whole = s->filled & ~63u;
+  if (whole > s->hashed && whole - s->hashed >= r->stride) set_due(r, *s, true);
+  return 0;
+}
+
+int bt_sha1_dgram_slots_commit(bt_sha1_intake *rr, uint8_t *slot, const uint8_t expected[20], uint64_t tag) {
+  Intake *r = impl(rr);
+  if (!r || !slot || !expected) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (wrong_kind(r, true, "commit_gather")) return -1;
+  ISlot *s = locate(r, slot);
+  if (!s) return -1;
+  if (s->filled == 0) {
+    set_err("gather intake: commit of a slot with no bytes listed");
+    return -1;
+  }
+  commit_slot(r, s, s->filled, expected, tag);
   return 0;
 }
 

@@ -500,6 +500,33 @@ int bt_sha1_resume_dev(const void *d_base, const uint64_t *d_offsets, const uint
   return 0;
 }
 
+int bt_sha1_dgram_chain_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_pos,
+                            const uint64_t *d_seg_first, const uint32_t *d_seg_count, const uint64_t *d_from,
+                            const uint32_t *d_lens, const uint64_t *d_totals, uint64_t n, uint32_t *d_states,
+                            uint8_t *d_digests, const uint8_t *d_expected, uint8_t *d_ok, void *stream) {
+  if (n == 0) return 0;
+  if (!d_base || !d_segs || !d_seg_pos || !d_seg_first || !d_seg_count || !d_from || !d_lens || !d_totals ||
+      !d_states) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (d_ok && !d_expected) {
+    set_err("null pointer: d_ok needs d_expected");
+    return -1;
+  }
+  if (n > BTSHA1_RESUME_MAX) {  // one workgroup per message
+    set_err("gather resume: %llu messages exceed the grid limit of %llu per launch", (unsigned long long)n,
+            (unsigned long long)BTSHA1_RESUME_MAX);
+    return -1;
+  }
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  if (!ctx_for(dev)) return -1;
+  BT_CK(btsha1_launch_gather_resume(d_base, d_segs, d_seg_pos, d_seg_first, d_seg_count, d_from, d_lens, d_totals, n,
+                                    d_states, d_digests, d_expected, d_ok, pick_stream(stream)));
+  return 0;
+}
+
 int bt_sha1_fill_synthetic(void *d_buf, uint64_t nbytes, uint64_t first_word, uint64_t seed, void *stream) {
   if (nbytes && (!d_buf || ((uintptr_t)d_buf & 15))) {
     set_err("fill needs a non-null 16-byte aligned buffer");

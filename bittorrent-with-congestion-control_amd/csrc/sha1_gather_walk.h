@@ -259,4 +259,149 @@ BT_GATHER_HD uint32_t gather_walk(GatherCursor &c, uint32_t (&w)[16], Sink &sink
   }
 }
 
+// ---------------------------------------------------------------------------
+// Random access, for the chain-form gather kernels (k_sha1_gather_resume):
+// their S wave has lane j build block b0 + j of ONE message, 64 blocks side by
+// side, so every lane has to find the segment that holds its block's first
+// byte.  pos[k] is the message position of segment k's first byte (the sum of
+// the lengths before it), parallel to segs.  The contract above is kept and
+// extended: no byte outside the listed segments is read, and NO DESCRIPTOR OR
+// pos ENTRY AT INDEX >= nseg IS READ (the host may be appending there while
+// the launch runs).
+// ---------------------------------------------------------------------------
+
+// The segment that holds message byte m (m below the listed total): the
+// largest k < nseg with pos[k] <= m; among empty segments that share a
+// position that is the one with bytes in it.  Gallops forward from `hint`
+// (1, 2, 4, ... entries), then bisects the last stride: with 1484-byte
+// payloads a block of the batch that `hint` was taken for lies at most three
+// segments on, found with three dependent reads, where a bisection of the
+// whole list would take nine.  Any hint gives the same answer: one at or past
+// nseg, or past the segment sought, restarts the search from segment 0.
+BT_GATHER_HD uint32_t gather_seek_seg(const uint64_t *pos, uint32_t nseg, uint64_t m, uint32_t hint) {
+  uint32_t lo = hint < nseg ? hint : 0u;
+  lo = pos[lo] <= m ? lo : 0u;
+  uint32_t step = 1u, hi = nseg;  // pos[lo] <= m; pos[hi] > m, or hi == nseg
+  while (lo + step < nseg) {
+    const uint32_t k = lo + step;
+    if (pos[k] > m) {
+      hi = k;
+      break;
+    }
+    lo = k;
+    step += step;
+  }
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (pos[mid] <= m) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// A cursor standing at message byte m (below the listed total), as the walk
+// would have left it there; returns the segment through *seg for the next hint.
+BT_GATHER_HD void gather_seek(GatherCursor &c, const uint8_t *base, const GatherSeg *segs, const uint64_t *pos,
+                              uint32_t nseg, uint64_t m, uint32_t hint, uint32_t *seg) {
+  const uint32_t k = gather_seek_seg(pos, nseg, m, hint);
+  const GatherSeg s = gather_seg(segs + k);
+  const uint32_t in = (uint32_t)(m - pos[k]);
+  c.base = base;
+  c.segs = segs;
+  c.nseg = nseg;
+  c.ja = k;
+  c.pa = base + s.off + in;
+  c.ra = s.len - in;
+  c.la = s.len;
+  c.total = m;
+  gather_load_b(c);
+  *seg = k;
+}
+
+// gather_bytes with a bound: the next min(limit, what is listed) bytes,
+// limit <= 64, and not one byte more -- the r tail bytes of a finishing entry,
+// behind which further segments may already be listed.
+BT_GATHER_HD uint32_t gather_bytes_upto(GatherCursor &c, uint32_t (&w)[16], uint32_t limit) {
+  uint32_t got = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) w[j] = 0u;
+  // Rolled, unlike gather_bytes: the chain-form kernels carry this loop once
+  // per instantiation beside their round wave, and its time hides behind R.
+  // The word goes into w through selects (a store at a variable index would
+  // put w into scratch memory).
+#pragma nounroll
+  for (uint32_t k = 0; k < 16u && got < limit; ++k) {
+    uint32_t v = 0;
+#pragma nounroll
+    for (uint32_t b = 0; b < 4; ++b) {
+      while (got < limit && c.ra == 0 && c.ja + 1 < c.nseg) {
+        const GatherSeg s = gather_seg(c.segs + ++c.ja);
+        c.pa = c.base + s.off;
+        c.ra = c.la = s.len;
+      }
+      if (got < limit && c.ra) {
+        v |= (uint32_t)*c.pa++ << (24u - 8u * b);
+        --c.ra;
+        ++got;
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) w[j] = gather_sel(j == k, v, w[j]);
+  }
+  c.total += got;
+  return got;
+}
+
+// "Block at position": the whole block at message bytes [m, m + 64), all of
+// them listed, as 16 big-endian words -- seek, then the walk's two ways to a
+// block.  The regular way's loads stay clamped inside A and B; its trailing
+// descriptor load (the cursor's next B) is clamped below nseg like the walk's.
+BT_GATHER_HD void gather_block_at(uint32_t (&w)[16], const uint8_t *base, const GatherSeg *segs, const uint64_t *pos,
+                                  uint32_t nseg, uint64_t m, uint32_t hint, uint32_t *seg) {
+  GatherCursor c;
+  gather_seek(c, base, segs, pos, nseg, m, hint, seg);
+  if (gather_regular(c)) {
+    GatherPlan p;
+    GatherSlot s;
+    gather_plan(c, p);
+    gather_fetch(s, p);
+    gather_words(w, s);
+  } else {
+    gather_bytes_upto(c, w, 64u);
+  }
+}
+
+// Both in one: the `want` bytes (1 .. 64, all listed) at [m, m + want) as
+// big-endian words, zero past them -- a whole block by the regular path where
+// it applies, anything else by bytes.  One seek and one copy of each path for
+// a caller (the chain-form kernels' S wave) that builds blocks and tails alike.
+BT_GATHER_HD void gather_span_at(uint32_t (&w)[16], const uint8_t *base, const GatherSeg *segs, const uint64_t *pos,
+                                 uint32_t nseg, uint64_t m, uint32_t want, uint32_t hint, uint32_t *seg) {
+  GatherCursor c;
+  gather_seek(c, base, segs, pos, nseg, m, hint, seg);
+  if (want == 64u && gather_regular(c)) {
+    GatherPlan p;
+    GatherSlot s;
+    gather_plan(c, p);
+    gather_fetch(s, p);
+    gather_words(w, s);
+  } else {
+    gather_bytes_upto(c, w, want);
+  }
+}
+
+// The r < 64 bytes at [m, m + r) (listed; r == 0 reads nothing, and m may then
+// be the listed total) as big-endian words, zero past them: the tail of a
+// finishing entry before the 0x80 mark goes in.
+BT_GATHER_HD void gather_tail_at(uint32_t (&w)[16], const uint8_t *base, const GatherSeg *segs, const uint64_t *pos,
+                                 uint32_t nseg, uint64_t m, uint32_t r, uint32_t hint) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) w[k] = 0u;
+  if (r == 0) return;
+  GatherCursor c;
+  uint32_t seg;
+  gather_seek(c, base, segs, pos, nseg, m, hint, &seg);
+  gather_bytes_upto(c, w, r);
+}
+
 }  // namespace btsha1

@@ -34,6 +34,9 @@
 //   k_sha1_gather / k_sha1_gather_verify  messages given as lists of segments
 //                   (a chunk hashed where its datagrams landed), one message
 //                   per lane; the segment walk is sha1_gather_walk.h.
+//   k_sha1_gather_resume / k_sha1_gather_resume_table  k_sha1_resume's S / R
+//                   split over a segment list that is still growing: S seeks
+//                   each block's segment (a chunk hashed while its datagrams arrive).
 //   k_fill_synthetic  frozen counter-based generator (bench/test data in HBM).
 //   k_lookup_build / k_lookup_query  digest -> first index table in HBM
 //                   (get_chunk_id / find_chunk, util.c:3-39).
@@ -1593,6 +1596,181 @@ __global__ __launch_bounds__(kBlock) void k_lookup_query(const uint8_t *__restri
   index[q] = r;
 }
 
+// ---------------------------------------------------------------------------
+// Chain-form gather, resumable: k_sha1_resume's S / R split over a message
+// given as a segment list that is still growing -- a chunk received as
+// datagrams, hashed in place over the in-sequence prefix that has arrived
+// (bt_sha1_gather_resume_dev; the gather intake, bt_intake.cpp).  One two-wave
+// workgroup per message.  R, the two 21 KiB LDS slots, produce_wk, the
+// advance-or-finish decision and the barrier count are k_sha1_resume's; only
+// where S takes a block from differs:
+//   block g below the len >> 6 whole blocks is built by lane g & 63 as "block
+//           at position from + 64 g" (gather_span_at, sha1_gather_walk.h):
+//           a seek through pos[], galloping from the segment that held the
+//           previous batch's last block (wave-uniform; with 1484-byte payloads
+//           at most three entries on), then the walk's regular or byte path
+//   padding blocks as chain_block<false> lays them out: the r tail bytes come
+//           through the same gather_span_at (r bytes, not one more), the bit
+//           count from total
+//   lanes past the end build a block of zeros and read nothing
+// No byte outside the nseg listed segments is read, and no descriptor or pos
+// entry at index >= nseg: the host may be appending there during the launch.
+// from is a 64-byte multiple and [from, from + len) lies inside the listed
+// bytes.  Whether a message advances or finishes is workgroup-uniform; both
+// waves execute nbatch + 1 barriers, nbatch = ceil(nb / 64), nb = len >> 6
+// for an advance and (len >> 6) + (r >= 56 ? 2 : 1) for a finish.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void gather_chain_block(uint32_t (&w)[16], const uint8_t *base, const GatherSeg *segs,
+                                                   const uint64_t *pos, uint32_t nseg, uint64_t from, uint64_t g,
+                                                   uint64_t nfull, uint32_t r, uint64_t bits, bool fin, uint32_t hint,
+                                                   uint32_t &seg) {
+  // One seek serves a whole block and the tail: `want` bytes at from + 64 g.
+  const bool tail = fin && g == nfull;
+  const uint32_t want = g < nfull ? 64u : (tail ? r : 0u);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) w[j] = 0u;
+  if (want) gather_span_at(w, base, segs, pos, nseg, from + 64ull * g, want, hint, &seg);
+  if (tail) {  // 0x80 behind the tail bytes (+ the length when r <= 55)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] |= (uint32_t)j == (r >> 2) ? 0x80000000u >> ((r & 3u) * 8u) : 0u;
+  }
+  if (fin && (tail ? r < 56u : g == nfull + 1u)) {  // the bit count: in the tail block, or alone when r >= 56
+    w[14] = (uint32_t)(bits >> 32);
+    w[15] = (uint32_t)bits;
+  }
+}
+
+// dig / exp / okp: where this message's digest (may be NULL), expected hash
+// and verdict live; done (may be NULL) gets seq after the results.
+template <bool VERIFY>
+__device__ __forceinline__ void gather_resume_body(u32x4 (*lds)[kChainStride * kChainBatch], const uint8_t *base,
+                                                   const GatherSeg *segs, const uint64_t *pos, uint32_t nseg,
+                                                   uint32_t hint0, uint64_t from, uint32_t len, uint64_t total,
+                                                   uint32_t *st_io, uint8_t *dig, const uint8_t *exp, uint8_t *okp,
+                                                   uint32_t *done, uint32_t seq) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool fin = total != 0;  // workgroup-uniform: both waves agree
+  const uint64_t nfull = len >> 6;
+  const uint32_t r = len & 63u;
+  const uint64_t nb_total = fin ? nfull + (r >= 56u ? 2u : 1u) : nfull;
+  const uint64_t nbatch = (nb_total + kChainBatch - 1) / kChainBatch;
+  uint32_t nbar = 0;
+  (void)nbar;
+  if (wave == 0) {
+    // ---- S: lane j prepares block b0 + j ----------------------------------
+    uint32_t hint = hint0;
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const uint64_t g = bt * kChainBatch + lane;
+      const uint64_t gc = g < nb_total ? g : nb_total + 1u;  // lanes past the end: a block that reads nothing
+      uint32_t w[16], seg = hint;
+      gather_chain_block(w, base, segs, pos, nseg, from, gc, nfull, r, total * 8ull, fin, hint, seg);
+      // The next batch starts one block past lane 63's: its segment is the hint.
+      hint = (uint32_t)__builtin_amdgcn_readlane((int)seg, 63);
+      produce_wk<0, 80, 1, kChainStride>(w, lds[bt & 1u], lane);
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_BARRIER(nbar);  // pairs with R's last barrier
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+  } else {
+    // ---- R: the chain, from the state the last launch left ------------------
+    State st;
+    st.h0 = st_io[0]; st.h1 = st_io[1]; st.h2 = st_io[2]; st.h3 = st_io[3]; st.h4 = st_io[4];
+    BT_LAT_BARRIER(nbar);  // batch 0 is in slot 0
+    const uint32_t l16 = lane & 15u, l4 = lane & 3u;
+    for (uint64_t bt = 0; bt < nbatch; ++bt) {
+      const u32x4 *slot = lds[bt & 1u];
+      const uint64_t left = nb_total - bt * kChainBatch;
+      const uint32_t nb = left < kChainBatch ? (uint32_t)left : kChainBatch;
+      // Block k+1's two reads are issued before block k's rounds.
+      u32x4 A = slot[l16], B = slot[16 + l4];
+      for (uint32_t k = 0; k < nb; ++k) {
+        const u32x4 *nxt = slot + (k + 1 < nb ? k + 1 : k) * kChainStride;
+        const u32x4 An = nxt[l16], Bn = nxt[16 + l4];
+        chain_rounds(st, A, B);
+        A = An;
+        B = Bn;
+      }
+      BT_LAT_BARRIER(nbar);
+    }
+    BT_LAT_CHECK(nbar, nbatch + 1u);
+    if (lane == 0) {
+      if (!fin) {
+        st_io[0] = st.h0; st_io[1] = st.h1; st_io[2] = st.h2; st_io[3] = st.h3; st_io[4] = st.h4;
+      } else {
+        const uint32_t h[5] = {st.h0, st.h1, st.h2, st.h3, st.h4};
+        if (dig) {
+#pragma unroll
+          for (int k = 0; k < 5; ++k) {  // sha.c:550-553
+            dig[4 * k] = (uint8_t)(h[k] >> 24);
+            dig[4 * k + 1] = (uint8_t)(h[k] >> 16);
+            dig[4 * k + 2] = (uint8_t)(h[k] >> 8);
+            dig[4 * k + 3] = (uint8_t)h[k];
+          }
+        }
+        if constexpr (VERIFY) {  // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+          uint32_t diff = 0;
+#pragma unroll
+          for (int k = 0; k < 20; ++k) diff |= (uint32_t)exp[k] ^ ((h[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu);
+          *okp = diff == 0;
+        }
+      }
+      // Completion word, as k_sha1_resume's: released at system scope after the results.
+      if (done) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// The array form (bt_sha1_gather_resume_dev): blockIdx.x = message i, whose
+// listed segments are segs[seg_first[i] .. + seg_count[i]) with pos parallel
+// to segs; bytes [from[i], from[i] + lens[i]) of it are hashed into
+// states[5*i ..].  totals[i] == 0 advances, else finishes: digest i to digests
+// + 20*i (digests may be NULL) and, with VERIFY, ok[i]; entries of advancing
+// messages are left alone.
+template <bool VERIFY>
+__global__ __launch_bounds__(128) void k_sha1_gather_resume(const uint8_t *__restrict__ base,
+                                                            const GatherSeg *__restrict__ segs,
+                                                            const uint64_t *__restrict__ pos,
+                                                            const uint64_t *__restrict__ seg_first,
+                                                            const uint32_t *__restrict__ seg_count,
+                                                            const uint64_t *__restrict__ from,
+                                                            const uint32_t *__restrict__ lens,
+                                                            const uint64_t *__restrict__ totals,
+                                                            uint32_t *__restrict__ states, uint8_t *__restrict__ digests,
+                                                            const uint8_t *__restrict__ expected,
+                                                            uint8_t *__restrict__ ok) {
+  __shared__ u32x4 lds[2][kChainStride * kChainBatch];  // as k_sha1_chain: 2 slots x 64 blocks, 42 KiB
+  const uint64_t i = blockIdx.x;
+  const uint64_t first = seg_first[i];
+  gather_resume_body<VERIFY>(lds, base, segs + first, pos + first, seg_count[i], 0u, from[i], lens[i], totals[i],
+                             states + 5 * i, digests ? digests + 20 * i : nullptr, VERIFY ? expected + 20 * i : nullptr,
+                             VERIFY ? ok + i : nullptr, nullptr, 0u);
+}
+
+// The table form (the gather intake): blockIdx.x = entry w of a table in
+// pinned host memory (BtSha1GatherEntry, sha1_launch.h), as k_sha1_resume_table
+// reads its own.  Slot `slot` has its bytes at slots + slot * pitch, its
+// descriptors at segs + slot * max_segs, their positions at pos + slot *
+// max_segs (of which the entry's nseg, those listed at kick time, are read)
+// and k_sha1_resume_table's 128-byte control block at ctl + slot * 128: state
+// and expected hash in line 0; digest, verdict and completion word in line 1.
+// seg_hint is the segment that holds `from`.  The entry's seq is stored into
+// the completion word with a system-scope release after the results.
+template <bool VERIFY>
+__global__ __launch_bounds__(128) void k_sha1_gather_resume_table(const BtSha1GatherEntry *__restrict__ table,
+                                                                  const uint8_t *__restrict__ slots, uint64_t pitch,
+                                                                  const GatherSeg *__restrict__ segs,
+                                                                  const uint64_t *__restrict__ pos, uint32_t max_segs,
+                                                                  uint8_t *__restrict__ ctl) {
+  __shared__ u32x4 lds[2][kChainStride * kChainBatch];  // as k_sha1_chain: 2 slots x 64 blocks, 42 KiB
+  const BtSha1GatherEntry ent = table[blockIdx.x];
+  uint8_t *cb = ctl + (uint64_t)ent.slot * BTSHA1_TABLE_CTL;
+  const uint64_t first = (uint64_t)ent.slot * max_segs;
+  gather_resume_body<VERIFY>(lds, slots + (uint64_t)ent.slot * pitch, segs + first, pos + first, ent.nseg, ent.seg_hint,
+                             ent.from, ent.len, ent.total, reinterpret_cast<uint32_t *>(cb), cb + 64, cb + 20, cb + 84,
+                             reinterpret_cast<uint32_t *>(cb + 88), ent.seq);
+}
+
 }  // namespace btsha1
 
 // ---------------------------------------------------------------------------
@@ -1961,6 +2139,38 @@ hipError_t btsha1_launch_resume_table(const BtSha1TableEntry *table, uint32_t n,
     hipLaunchKernelGGL(k_sha1_resume_table<true>, dim3(n), dim3(128), 0, s, table, slots, pitch, ctl);
   else
     hipLaunchKernelGGL(k_sha1_resume_table<false>, dim3(n), dim3(128), 0, s, table, slots, pitch, ctl);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_gather_resume(const void *base, const void *segs, const uint64_t *seg_pos,
+                                       const uint64_t *seg_first, const uint32_t *seg_count, const uint64_t *from,
+                                       const uint32_t *lens, const uint64_t *totals, uint64_t n, uint32_t *states,
+                                       uint8_t *digests, const uint8_t *expected, uint8_t *ok, hipStream_t s) {
+  if (n == 0 || n > BTSHA1_RESUME_MAX || !base || !segs || !seg_pos || !seg_first || !seg_count || !from || !lens ||
+      !totals || !states || (ok && !expected))
+    return hipErrorInvalidValue;
+  if (ok)
+    hipLaunchKernelGGL(k_sha1_gather_resume<true>, dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_pos, seg_first, seg_count, from, lens, totals, states, digests,
+                       expected, ok);
+  else
+    hipLaunchKernelGGL(k_sha1_gather_resume<false>, dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_pos, seg_first, seg_count, from, lens, totals, states, digests,
+                       expected, ok);
+  return hipGetLastError();
+}
+
+hipError_t btsha1_launch_gather_resume_table(const BtSha1GatherEntry *table, uint32_t n, const uint8_t *slots,
+                                             uint64_t pitch, const void *segs, const uint64_t *seg_pos,
+                                             uint32_t max_segs, uint8_t *ctl, bool verify, hipStream_t s) {
+  if (n == 0 || n > BTSHA1_TABLE_MAX || max_segs == 0 || !table || !slots || !segs || !seg_pos || !ctl)
+    return hipErrorInvalidValue;
+  if (verify)
+    hipLaunchKernelGGL(k_sha1_gather_resume_table<true>, dim3(n), dim3(128), 0, s, table, slots, pitch,
+                       (const GatherSeg *)segs, seg_pos, max_segs, ctl);
+  else
+    hipLaunchKernelGGL(k_sha1_gather_resume_table<false>, dim3(n), dim3(128), 0, s, table, slots, pitch,
+                       (const GatherSeg *)segs, seg_pos, max_segs, ctl);
   return hipGetLastError();
 }
 

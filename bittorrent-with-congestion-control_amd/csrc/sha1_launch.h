@@ -137,6 +137,46 @@ static_assert(sizeof(BtSha1TableEntry) == 32 && alignof(BtSha1TableEntry) == 32,
 #define BTSHA1_TABLE_CTL 128u
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_table(const BtSha1TableEntry *table, uint32_t n, const uint8_t *slots,
                                                     uint64_t pitch, uint8_t *ctl, bool verify, hipStream_t s);
+// Chain-form gather, resumable (k_sha1_gather_resume; one two-wave workgroup
+// per message): message i's listed segments are segs[seg_first[i] .. +
+// seg_count[i]) (bt_sha1_seg, as btsha1_launch_gather's), seg_pos parallel to
+// segs (seg_pos[seg_first[i] + k] = the sum of the lengths of message i's
+// segments before k).  Bytes [from[i], from[i] + lens[i]) of the message
+// (from[i] a 64-byte multiple, the range inside the listed bytes) are hashed
+// into states[5*i ..]; totals / digests / expected / ok as
+// btsha1_launch_resume's.  No byte outside the listed segments and no table
+// entry past a message's listed ones is read.  hipErrorInvalidValue and no
+// launch for a null base or table, n == 0 or n above BTSHA1_RESUME_MAX (the
+// grid), or ok without expected.
+BTSHA1_HIDDEN hipError_t btsha1_launch_gather_resume(const void *base, const void *segs, const uint64_t *seg_pos,
+                                                     const uint64_t *seg_first, const uint32_t *seg_count,
+                                                     const uint64_t *from, const uint32_t *lens,
+                                                     const uint64_t *totals, uint64_t n, uint32_t *states,
+                                                     uint8_t *digests, const uint8_t *expected, uint8_t *ok,
+                                                     hipStream_t s);
+// Its table-driven form (k_sha1_gather_resume_table; the gather intake of
+// bt_intake.cpp): workgroup w serves entry w of `table` (pinned host memory):
+// message bytes [from, from + len) of slot `slot`, whose datagrams lie at
+// slots + slot * pitch, whose descriptors at segs + slot * max_segs and their
+// positions at seg_pos + slot * max_segs; nseg of them were listed when the
+// entry was made and only those are read; seg_hint is the segment that holds
+// `from`.  total, seq and the control block at ctl + slot * BTSHA1_TABLE_CTL
+// are btsha1_launch_resume_table's.  hipErrorInvalidValue and no launch for
+// n == 0, n > BTSHA1_TABLE_MAX, max_segs == 0 or a null base.
+struct alignas(32) BtSha1GatherEntry {
+  uint32_t slot;
+  uint32_t from, len;
+  uint32_t total;     // 0: advance; else the chunk's length (at most 32 MiB)
+  uint32_t seq;
+  uint32_t nseg;      // segments listed at kick time
+  uint32_t seg_hint;  // the segment that holds `from`
+  uint32_t pad;
+};
+static_assert(sizeof(BtSha1GatherEntry) == 32 && alignof(BtSha1GatherEntry) == 32, "gather table entry layout");
+BTSHA1_HIDDEN hipError_t btsha1_launch_gather_resume_table(const BtSha1GatherEntry *table, uint32_t n,
+                                                           const uint8_t *slots, uint64_t pitch, const void *segs,
+                                                           const uint64_t *seg_pos, uint32_t max_segs, uint8_t *ctl,
+                                                           bool verify, hipStream_t s);
 // d_states[5*i ..] = the SHA-1 IV (sha.c:149-163) for i < n.
 BTSHA1_HIDDEN hipError_t btsha1_launch_states_init(uint32_t *d_states, uint64_t n, hipStream_t s);
 // One column of n equal chunks (k_sha1_lat's column forms): chunk i's column

@@ -208,6 +208,39 @@ int bt_sha1_states_init_dev(uint32_t *d_states, uint64_t n, void *stream);
 int bt_sha1_resume_dev(const void *d_base, const uint64_t *d_offsets, const uint32_t *d_lens,
                        const uint64_t *d_totals, uint64_t n, uint32_t *d_states, uint8_t *d_digests,
                        const uint8_t *d_expected, uint8_t *d_ok, void *stream);
+/* The two together: resumable hashing of messages given as SEGMENT LISTS that
+ * are still growing -- a chunk received as datagrams, hashed where recvfrom put
+ * them over the in-sequence prefix that has arrived (the chain-form gather
+ * kernel: one two-wave workgroup per message, the latency form; with d_from =
+ * 0 and d_lens = d_totals it is gather's latency form for a handful of whole
+ * chunks).  Message i's segments listed so far are d_segs[d_seg_first[i] .. +
+ * d_seg_count[i]); d_seg_pos is parallel to d_segs: the entry of message i's
+ * segment k is the sum of the lengths of its segments before k.  The launch
+ * hashes message bytes [d_from[i], d_from[i] + d_lens[i]) into d_states[5*i ..].
+ * The caller keeps: d_from[i] a 64-byte multiple; the range inside the listed
+ * bytes; for a finish (d_totals[i] != 0), d_from[i] + d_lens[i] == d_totals[i].
+ * No byte outside the listed segments is read, and no entry of d_segs /
+ * d_seg_pos past a message's listed ones, so the caller may be appending
+ * there.  States, d_totals, d_digests / d_expected / d_ok, null handling and
+ * the bound on n are exactly bt_sha1_resume_dev's; data and tables may be
+ * device or pinned host memory.
+ * The library exports this function as bt_sha1_dgram_chain_dev (its export
+ * lists close the gather_ and resume_ name families at the functions above);
+ * bt_sha1_gather_resume_dev is the same call under the name it is known by. */
+int bt_sha1_dgram_chain_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_pos,
+                            const uint64_t *d_seg_first, const uint32_t *d_seg_count,
+                            const uint64_t *d_from, const uint32_t *d_lens, const uint64_t *d_totals,
+                            uint64_t n, uint32_t *d_states, uint8_t *d_digests /* may be NULL */,
+                            const uint8_t *d_expected, uint8_t *d_ok, void *stream);
+static inline int bt_sha1_gather_resume_dev(const void *d_base, const bt_sha1_seg *d_segs,
+                                            const uint64_t *d_seg_pos, const uint64_t *d_seg_first,
+                                            const uint32_t *d_seg_count, const uint64_t *d_from,
+                                            const uint32_t *d_lens, const uint64_t *d_totals, uint64_t n,
+                                            uint32_t *d_states, uint8_t *d_digests /* may be NULL */,
+                                            const uint8_t *d_expected, uint8_t *d_ok, void *stream) {
+  return bt_sha1_dgram_chain_dev(d_base, d_segs, d_seg_pos, d_seg_first, d_seg_count, d_from, d_lens, d_totals, n,
+                                 d_states, d_digests, d_expected, d_ok, stream);
+}
 /* Frozen generator: 64-bit word g of the stream = splitmix64(seed + g), LE.
  * Writes words first_word .. into d_buf (16-byte aligned), nbytes bytes. */
 int bt_sha1_fill_synthetic(void *d_buf, uint64_t nbytes, uint64_t first_word, uint64_t seed,
@@ -521,6 +554,56 @@ int bt_sha1_intake_drain(bt_sha1_intake *r, bt_sha1_verdict *out, int max);
 /* Verdicts not yet returned (recorded + in flight + finished-unpolled). */
 int64_t bt_sha1_intake_pending(bt_sha1_intake *r);
 int bt_sha1_intake_get_stats(bt_sha1_intake *r, bt_sha1_intake_stats *out);
+/* A GATHER intake: the same object and life cycle, but a slot holds DATAGRAMS
+ * where recvfrom / recvmmsg put them (as the gather verifier's slots), and the
+ * chunk is hashed in place over the in-sequence prefix of payloads that has
+ * arrived: no memcpy into place (util.c:275), and at commit only the last
+ * stride and the padding are left.  kick launches the table-driven chain-form
+ * gather kernel; the eight-table ring, the four streams and `deferred` are as
+ * above, and slot, release, kick, sync, poll, drain, pending and get_stats work
+ * unchanged.  A slot's segment list is empty, and its state the IV, whenever it
+ * is handed out.
+ * create_gather: slot_len 1 .. 33 MiB (the pitch is slot_len rounded up to 16);
+ *   max_segs >= 1 segments per chunk at most; nslots 1..512; nslots x pitch at
+ *   most 2 GiB and nslots x max_segs x 24 bytes of pinned segment tables at
+ *   most 256 MiB; stride as above.  NULL with a message for arguments out of
+ *   range, before any device call.
+ * append: the NEXT nseg payload segments in sequence order (off relative to
+ *   the slot): the caller holds an out-of-order datagram back until the gap
+ *   before it is filled, and never lists a duplicate.  Records only; the slot
+ *   is due once the listed whole blocks not yet hashed reach `stride`.  More
+ *   than max_segs segments in total, a segment with off + len > slot_len, or a
+ *   running total above 32 MiB, is -1 with a message: nothing is recorded and
+ *   the intake stays usable.  Legal while a launch on the slot is in flight
+ *   (entries carry the segment count of kick time; the kernel reads no
+ *   descriptor at or past it).
+ * commit_gather: the chunk is complete at the bytes listed (more than 0): the
+ *   next kick that finds the slot without a launch in flight queues ONE
+ *   finishing entry over everything not yet hashed, the compare fused.
+ * bt_sha1_intake_advance / _commit are refused on a gather intake, append /
+ * commit_gather on a plain one, with a message.
+ * The library exports the three as bt_sha1_dgram_slots_create / _append /
+ * _commit (its export lists close the intake_ name family at the functions
+ * above); the bt_sha1_intake_ names below are the same calls. */
+bt_sha1_intake *bt_sha1_dgram_slots_create(int device, uint32_t slot_len, uint32_t max_segs,
+                                           uint32_t nslots, uint32_t stride);
+int bt_sha1_dgram_slots_append(bt_sha1_intake *r, uint8_t *slot, const bt_sha1_seg *segs,
+                               uint32_t nseg);
+int bt_sha1_dgram_slots_commit(bt_sha1_intake *r, uint8_t *slot, const uint8_t expected[20],
+                               uint64_t tag);
+static inline bt_sha1_intake *bt_sha1_intake_create_gather(int device, uint32_t slot_len,
+                                                           uint32_t max_segs, uint32_t nslots,
+                                                           uint32_t stride) {
+  return bt_sha1_dgram_slots_create(device, slot_len, max_segs, nslots, stride);
+}
+static inline int bt_sha1_intake_append(bt_sha1_intake *r, uint8_t *slot, const bt_sha1_seg *segs,
+                                        uint32_t nseg) {
+  return bt_sha1_dgram_slots_append(r, slot, segs, nseg);
+}
+static inline int bt_sha1_intake_commit_gather(bt_sha1_intake *r, uint8_t *slot,
+                                               const uint8_t expected[20], uint64_t tag) {
+  return bt_sha1_dgram_slots_commit(r, slot, expected, tag);
+}
 
 /* ---- digest lookup (get_chunk_id / find_chunk, util.c:3-39, on the GPU) - */
 /* d_index[q] = smallest i with digest d_table[i] == d_queries[q], else -1.

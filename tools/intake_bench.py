@@ -26,6 +26,11 @@ One process, so the rows compare on one box.  One JSON line per row:
                      table kernel's single finishing entry (kick -> sync, wall),
                      the receiver's single launch at stride NEVER (commit ->
                      drain, wall), k_sha1_resume (events) and shahash (wall)
+--gather: the same rows with DATAGRAM slots (bt.Intake(gather=True)): every
+64 KiB piece is landed as its 1500-byte datagrams (16-byte header, 1484-byte
+payload) and appended; sustained_gather_intake_<n>, then latency_bench's
+gather rows (one finishing entry over 354 datagrams against the contiguous
+table kernel, commit -> verdict at the default stride).
 Digests are checked against the oracle (hashlib is not used).
 """
 import argparse
@@ -46,9 +51,10 @@ CHUNK = 512 * 1024
 PIECE = 64 * 1024
 
 
-def feed(obj, nslots, nchunks, addr, want, commit=True):
+def feed(obj, nslots, nchunks, addr, want, commit=True, copy=True):
     """Round-robin feed of nchunks chunks over nslots slots; returns seconds
-    from the first byte to the last verdict (commit) or to the last byte."""
+    from the first byte to the last verdict (commit) or to the last byte.
+    copy=False: obj.advance lands the bytes itself (DatagramFeed)."""
     todo, free, got = nchunks, nslots, 0
     active = []  # [slot, bytes delivered]
     tag = 0
@@ -61,7 +67,8 @@ def feed(obj, nslots, nchunks, addr, want, commit=True):
         still = []
         for a in active:
             p, o = a
-            ctypes.memmove(p + o, addr + o, PIECE)
+            if copy:
+                ctypes.memmove(p + o, addr + o, PIECE)
             a[1] = o + PIECE
             obj.advance(p, a[1])
             if a[1] < CHUNK:
@@ -96,6 +103,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50, help="repetitions of the latency rows")
     ap.add_argument("--only", choices=["all", "latency"], default="all")
+    ap.add_argument("--gather", action="store_true", help="datagram slots: the gather intake's rows")
     ap.add_argument("--receiver-gib", type=float, default=None,
                     help="GiB per receiver run (default: --gib); its rate does not depend on the length")
     args = ap.parse_args()
@@ -113,6 +121,11 @@ def main():
     nchunks = int(args.gib * 2**30) // CHUNK
     gib = nchunks * CHUNK / 2**30
 
+    if args.gather:
+        if args.only == "all":
+            sustained_gather(bt, args, msg, want, nchunks, gib)
+        lb.gather_rows(bt, torch, msg, want, args.reps)
+        return
     if args.only == "all":
         sustained(bt, args, addr, want, nchunks, gib)
     latency(bt, lb, torch, args, addr, msg, want)
@@ -153,6 +166,57 @@ def sustained(bt, args, addr, want, nchunks, gib):
                       "beats_by_more_than_both_spreads":
                           i64["GiB_per_s"] - r["GiB_per_s"] > (r["max"] - r["min"]) + (i64["max"] - i64["min"]),
                       "ratio_512_over_64": round(rows[512]["GiB_per_s"] / i64["GiB_per_s"], 2)}), flush=True)
+
+
+class DatagramFeed:
+    """feed()'s view of a gather intake: a 64 KiB piece is landed as the
+    datagrams whose payloads end inside it, each appended as it lands."""
+    DGRAM, HEADER, PAYLOAD = 1500, 16, 1484
+
+    def __init__(self, ix, msg):
+        self.ix = ix
+        self.nd = -(-CHUNK // self.PAYLOAD)
+        self.pkts = [bytes(self.HEADER) + msg[k * self.PAYLOAD:(k + 1) * self.PAYLOAD] for k in range(self.nd)]
+        self.sent = {}
+
+    def slot(self):
+        p = self.ix.slot()
+        self.sent[p] = 0
+        return p
+
+    def advance(self, p, filled):
+        k = self.sent[p]
+        while k < self.nd and (min((k + 1) * self.PAYLOAD, CHUNK) <= filled):
+            ctypes.memmove(p + k * self.DGRAM, self.pkts[k], len(self.pkts[k]))
+            self.ix.append(p, [(k * self.DGRAM + self.HEADER, len(self.pkts[k]) - self.HEADER)])
+            k += 1
+        self.sent[p] = k
+
+    def commit(self, p, want, tag):
+        self.ix.commit_gather(p, want, tag)
+
+    def release(self, p):
+        self.ix.release(p)
+
+    def poll(self):
+        return self.ix.poll()
+
+
+def sustained_gather(bt, args, msg, want, nchunks, gib):
+    nd = -(-CHUNK // DatagramFeed.PAYLOAD)
+    for n in (64, 512):
+        ix = bt.Intake(chunk_len=nd * DatagramFeed.DGRAM, nslots=n, gather=True, max_segs=nd)
+        fd = DatagramFeed(ix, msg)
+        feed(fd, n, 2 * n, 0, want, copy=False)  # warm-up
+        before = ix.stats()
+        rates = [gib / feed(fd, n, nchunks, 0, want, copy=False) for _ in range(args.runs)]
+        s = ix.stats()
+        ix.close()
+        spread(f"sustained_gather_intake_{n}", rates,
+               {"GiB_per_run": gib, "max_entries": s["max_entries"],
+                "entries_per_launch": round((s["entries"] - before["entries"]) /
+                                            max(1, s["launches"] - before["launches"]), 1),
+                "deferred": s["deferred"] - before["deferred"]})
 
 
 def latency(bt, lb, torch, args, addr, msg, want):

@@ -27,6 +27,17 @@ one JSON line per measurement (median of --reps):
   receiver_first_byte_<stride>  the same delivery fed back to back with no
                     waiting: first byte -> verdict (what the extra launches
                     cost when the data is already there)
+  finish_gather_intake_512k, finish_intake_512k_same_session, ratio_gather_over_contiguous
+                         one finishing entry over a 512 KiB chunk held as 354
+                         datagrams (k_sha1_gather_resume_table, kick -> sync,
+                         wall) against k_sha1_resume_table over the same bytes
+                         contiguous, in this process; their ratio
+  commit_gather_intake_default, commit_intake_default_same_session,
+  verdict_gather_verifier_lone_chunk
+                         commit -> verdict of a chunk delivered as datagrams at
+                         network pace at the default stride, the assembled-slot
+                         intake's, and the gather verifier's flush -> verdict
+                         for a lone chunk (--only gather runs just these)
   resume_1x512k_<where>  one finishing launch of bt_sha1_resume_dev over a whole
                     512 KiB message from the IV, kernel time: the message in
                     device memory (dev) or read in place from pinned host
@@ -62,7 +73,7 @@ def emit(name, samples_s, extra=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--only", choices=["all", "receiver"], default="all")
+    ap.add_argument("--only", choices=["all", "receiver", "gather"], default="all")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -72,6 +83,11 @@ def main():
     rng = np.random.default_rng(7)
     msg = bytes(orc.fill_synthetic(CHUNK, 0, orc.SEED_SYNTH))
     want = orc.sha1(msg)
+    if args.only == "gather":
+        assert torch.cuda.is_available()
+        torch.zeros(1, device="cuda")  # torch's runtime first
+        gather_rows(bt, torch, msg, want, max(args.reps, 50))
+        return
     if args.only == "receiver":
         assert torch.cuda.is_available()
         torch.zeros(1, device="cuda")  # torch's runtime first
@@ -266,6 +282,104 @@ def resume_rows(bt, torch, msg, want, reps):
         ts.append(time.perf_counter() - t0)
     assert got == want
     emit("shahash_512k", ts[1:], {"kernel": "k_sha1_chain"})
+
+
+DGRAM, HEADER, PAYLOAD = 1500, 16, 1484
+
+
+def gather_rows(bt, torch, msg, want, reps):
+    """The chain-form gather kernel against its contiguous twin, in one process."""
+    import ctypes
+    nd = -(-CHUNK // PAYLOAD)
+    pkts = [bytes(HEADER) + msg[k * PAYLOAD:(k + 1) * PAYLOAD] for k in range(nd)]
+    segs = [(k * DGRAM + HEADER, len(pkts[k]) - HEADER) for k in range(nd)]
+    src = (ctypes.c_uint8 * CHUNK).from_buffer_copy(msg)
+
+    def land(p, k):
+        ctypes.memmove(p + k * DGRAM, pkts[k], len(pkts[k]))
+
+    def verdict(obj, tag):
+        while True:
+            got = obj.poll()
+            if got:
+                assert got == [(tag, True, want)], got
+                return
+
+    # (a) one finishing entry over the whole chunk, kick -> sync
+    med = {}
+    for name in ("gather_intake", "intake"):
+        gather = name == "gather_intake"
+        obj = bt.Intake(chunk_len=nd * DGRAM if gather else CHUNK, nslots=1, stride=bt.NEVER, gather=gather,
+                        max_segs=nd if gather else 0)
+        ts = []
+        for i in range(reps + 1):
+            p = obj.slot()
+            if gather:
+                for k in range(nd):
+                    land(p, k)
+                obj.append(p, segs)
+                obj.commit_gather(p, want, i)
+            else:
+                ctypes.memmove(p, ctypes.addressof(src), CHUNK)
+                obj.commit(p, want, i)
+            t0 = time.perf_counter()
+            assert obj.kick() == 1
+            obj.sync()
+            ts.append(time.perf_counter() - t0)
+            assert obj.drain() == [(i, True, want)]
+        obj.close()
+        med[name] = statistics.median(ts[1:])
+        emit(f"finish_{name}_512k" + ("" if gather else "_same_session"), ts[1:],
+             {"kernel": "k_sha1_gather_resume_table" if gather else "k_sha1_resume_table", "clock": "wall",
+              "datagrams": nd if gather else 0})
+    print(json.dumps({"case": "ratio_gather_over_contiguous",
+                      "ratio": round(med["gather_intake"] / med["intake"], 3)}), flush=True)
+
+    # (b) commit -> verdict at network pace, default stride
+    for name in ("gather_intake", "intake"):
+        gather = name == "gather_intake"
+        obj = bt.Intake(chunk_len=nd * DGRAM if gather else CHUNK, nslots=2, gather=gather, max_segs=nd if gather else 0)
+        ts = []
+        for i in range(reps + 1):
+            p = obj.slot()
+            for k in range(nd):
+                if gather:
+                    land(p, k)
+                    obj.append(p, [segs[k]])
+                else:
+                    o = k * PAYLOAD
+                    n = min(PAYLOAD, CHUNK - o)
+                    ctypes.memmove(p + o, ctypes.addressof(src) + o, n)
+                    obj.advance(p, o + n)
+                assert obj.poll() == []
+                obj.sync()  # the network's pace: a stride's launch ends long before the next stride has arrived
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if gather:
+                obj.commit_gather(p, want, i)
+            else:
+                obj.commit(p, want, i)
+            verdict(obj, i)
+            ts.append(time.perf_counter() - t0)
+        s = obj.stats()
+        obj.close()
+        emit(f"commit_{name}_default" + ("" if gather else "_same_session"), ts[1:],
+             {"launches_per_chunk": s["launches"] // (reps + 1),
+              "advanced_bytes_per_chunk": s["advanced_bytes"] // (reps + 1)})
+    v = bt.Verifier(chunk_len=nd * DGRAM, batch=1, nstreams=2, gather=True, max_segs=nd)
+    ts = []
+    for i in range(reps + 1):
+        p = v.slot()
+        for k in range(nd):
+            land(p, k)
+        t0 = time.perf_counter()
+        v.commit_gather(p, segs, want, i)
+        v.flush()
+        got = v.drain()
+        ts.append(time.perf_counter() - t0)
+        assert got == [(i, True, want)], got
+    v.close()
+    emit("verdict_gather_verifier_lone_chunk", ts[1:], {"kernel": "k_sha1_gather_verify"})
 
 
 def receiver_rows(bt, torch, msg, want, reps):
