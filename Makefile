@@ -33,7 +33,11 @@ HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_receiver 
 HOSTOBJ  := $(HOST:%=$(PKG)/build/%.o)
 KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/sha1_gather_walk.h
 HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/sha.h include/chunk.h
-SONAME   := -Wl,-soname,libbtsha1.so
+# The shipped builds carry no static symbol table (--strip-all: .dynsym stays,
+# the kernels' own symbols live inside the code object): 42 KB less in each,
+# part of what keeps the product under half the experiments library
+# (tests/test_abi.py).  The asan build keeps its symbols.
+SONAME   := -Wl,-soname,libbtsha1.so -Wl,--strip-all
 # One build of the library: $(call libbtsha1,object dir,library,kernel flags,
 # host flags,source id suffix,host objects besides bt_runtime.o,link flags)
 define libbtsha1
@@ -123,6 +127,15 @@ $(SEEKDIR)/gather_seek_check: tests/native/gather_seek_check.cpp $(CSRC)/sha1_ga
 	@mkdir -p $(SEEKDIR)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
 
+# The same for the stepper of the latency-form gather kernel (gather_step: one
+# block per call, padding included, nothing read past a message's end);
+# tests/test_gather_step_host.py builds and runs it too.
+STEPDIR  := build_variants/gather_step
+gather_step_check: $(STEPDIR)/gather_step_check
+$(STEPDIR)/gather_step_check: tests/native/gather_step_check.cpp $(CSRC)/sha1_gather_walk.h
+	@mkdir -p $(STEPDIR)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
+
 # Barrier-accounting build: the latency / chain / ragged-latency kernels count
 # the s_barriers each wave executes and check them against the invariant they
 # rely on (sha1_kernels.hip, "Barrier accounting"); bt_sha1_debug_barrier_stats
@@ -180,4 +193,4 @@ clean:
 	rm -rf $(PKG)/build $(LIB) $(BIN)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check gather_seek_check ubench sched_variants install clean
+.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check gather_seek_check gather_step_check ubench sched_variants install clean

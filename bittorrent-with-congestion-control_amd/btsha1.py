@@ -69,6 +69,8 @@ _sig("bt_sha1_build_info", ctypes.c_char_p)
 _sig("bt_sha1_set_ring_depth", ctypes.c_int, ctypes.c_int)
 _sig("bt_sha1_set_variant", ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)
 _sig("bt_sha1_set_latency_batch", _u64, _u64)
+_sig("bt_sha1_set_seglist_latency_batch", _u64, _u64)
+_sig("bt_sha1_seglist_kernel_name", ctypes.c_char_p, _u64)
 _sig("bt_sha1_chunks_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp)
 _sig("bt_sha1_verify_dev", ctypes.c_int, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_column_dev", ctypes.c_int, _vp, _u64, _u64, _u64, ctypes.c_int, _vp, _u64, _vp, _vp, _vp, _vp)
@@ -221,6 +223,17 @@ def set_latency_batch(max_chunks):
 def set_chain_batch(max_messages):
     """Ragged batches of <= max_messages take the chain kernel (0: never); returns the previous setting."""
     return lib.bt_sha1_set_chain_batch(max_messages)
+
+
+def set_seglist_latency_batch(max_messages):
+    """Segment-list batches of <= max_messages take k_sha1_gather_lat (0, the default: never;
+    2**64 - 1: 128 per CU); returns the previous setting."""
+    return lib.bt_sha1_set_seglist_latency_batch(max_messages)
+
+
+def seglist_kernel_name(n):
+    """Kernel a segment-list batch of n messages runs under the current setting and device."""
+    return lib.bt_sha1_seglist_kernel_name(n).decode()
 
 
 def build_info():

@@ -243,6 +243,14 @@ uint64_t bt_sha1_set_chain_batch(uint64_t max_messages) {
   return prev;
 }
 
+uint64_t bt_sha1_set_seglist_latency_batch(uint64_t max_messages) {
+  const uint64_t prev = btsha1_seglist_latency_batch_setting();
+  btsha1_set_seglist_latency_batch(max_messages);
+  return prev;
+}
+
+const char *bt_sha1_seglist_kernel_name(uint64_t n) { return btsha1_seglist_kernel_name(n); }
+
 const char *bt_sha1_kernel_name(uint64_t n_chunks) {
   if (device_count() <= 0) {
     set_err("no HIP device visible");

@@ -26,7 +26,8 @@
 //            segments in a block, empty segments, the message's tail): one
 //            byte load per byte, stepping over segments as they run out.
 // gather_walk() runs a message through both, keeping one regular block in
-// flight ahead of the block being consumed.
+// flight ahead of the block being consumed; gather_step() (below) does the
+// same one block per call, padding included, for k_sha1_gather_lat.
 #pragma once
 #include <stdint.h>
 
@@ -402,6 +403,137 @@ BT_GATHER_HD void gather_tail_at(uint32_t (&w)[16], const uint8_t *base, const G
   uint32_t seg;
   gather_seek(c, base, segs, pos, nseg, m, hint, &seg);
   gather_bytes_upto(c, w, r);
+}
+
+// ---------------------------------------------------------------------------
+// The stepper, for the latency-form gather kernel (k_sha1_gather_lat): its S
+// wave has lane j stream message j forward like gather_walk, but it meets the
+// round wave at one barrier per block, so every lane must yield EXACTLY ONE
+// block per call, in control flow the caller can keep wave-uniform --
+// gather_walk's loops have lane-dependent trip counts.  gather_step() yields
+// block b of the padded message (sha.c:529-543), one of
+//   regular   fetched by the call before (one block's loads stay in flight
+//             ahead of the block being produced, as in gather_walk);
+//   bytes     a whole block the regular path does not take;
+//   padding   the r tail bytes + 0x80, the 64-bit bit count in the last block
+//             (a block of its own when r >= 56);
+// and zeros, reading nothing, once the message is through (b >= nb).  The
+// contract above holds, with one addition: `idle` points to 16 readable bytes
+// of the CALLER's (any content).  The five loads of a block and its descriptor
+// load are issued on every call; a lane with no regular block next aims them
+// at `idle` instead of branching around them.  So a call for a lane past its
+// message, or for a message with no segments, reads `idle` and nothing else.
+// ---------------------------------------------------------------------------
+
+// The message's length: the 64-bit sum of its segment lengths, eight
+// descriptors per trip (indices clamped below nseg), so that the pass costs
+// nseg / 8 memory round trips and not nseg.
+BT_GATHER_HD uint64_t gather_total(const GatherSeg *segs, uint32_t nseg) {
+  uint64_t t = 0;
+  for (uint32_t j = 0; j < nseg; j += 8u) {
+    uint32_t l[8];
+#pragma unroll
+    for (uint32_t u = 0; u < 8u; ++u) l[u] = gather_seg(segs + (j + u < nseg ? j + u : nseg - 1u)).len;
+#pragma unroll
+    for (uint32_t u = 0; u < 8u; ++u) t += j + u < nseg ? l[u] : 0u;
+  }
+  return t;
+}
+
+struct GatherStepper {
+  GatherCursor c;  // behind the last block planned or taken by bytes
+  GatherSlot s;    // block b, fetched by the call before, when ahead
+  GatherSeg d;     // the descriptor that fetch asked for: the cursor's next B
+  uint32_t dsel;   // 0: keep the cursor's B; 1: none follows; 2: d
+  uint32_t ahead;
+  uint64_t b;          // the block the next call yields
+  uint64_t nfull, nb;  // whole blocks; blocks with the padding
+  uint64_t bits;
+  uint32_t r;
+};
+
+// gather_plan + gather_fetch where `go` (which needs gather_regular(c)), the
+// same six loads aimed at `idle` and the cursor left alone where not.
+//
+// The descriptor goes into the cursor one call later (gather_step_settle):
+// a select on it here would wait for it on the spot, one memory round trip
+// per block ahead of produce_block.
+BT_GATHER_HD void gather_fetch_if(GatherStepper &st, bool go, const uint8_t *idle) {
+  GatherCursor &c = st.c;
+  GatherSlot &s = st.s;
+  const uint32_t a = c.ra < 64u ? c.ra : 64u;
+  const bool cut = a < 64u;
+  const uint8_t *pb = cut ? c.base + c.boff : c.pa;
+  GatherPlan p;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) {
+    const uint32_t lo = 16u * i;
+    const uint8_t *in_a = c.pa + lo, *in_b = pb + lo - a, *win_a = c.pa + a - 16u;
+    const uint8_t *q = lo + 16u <= a ? in_a : (lo >= a ? in_b : win_a);
+    p.q[i] = go ? q : idle;
+  }
+  p.wb = go ? pb : idle;
+  p.c = a & 15u;
+  p.sq = go && cut && p.c ? a >> 4 : 4u;
+  const uint32_t into_b = cut ? 64u - a : 0u;
+  const bool step = go && (cut || c.ra == 64u);
+  const uint64_t boff = c.boff;
+  // The descriptor first, as in gather_plan: waiting for it never waits for
+  // the block's own loads.
+  const uint32_t jb = c.ja + (step ? 2u : 1u);
+  const bool has_b = go && jb < c.nseg;
+  const uint32_t kb = has_b ? jb : (go ? c.nseg - 1u : 0u);
+  __builtin_memcpy(&st.d, go ? (const uint8_t *)(c.segs + kb) : idle, sizeof st.d);
+  st.dsel = go ? (has_b ? 2u : 1u) : 0u;
+  gather_fetch(s, p);
+  c.total += go ? 64u : 0u;
+  c.pa = step ? c.base + boff + into_b : c.pa + (go ? 64u : 0u);
+  c.ra = step ? c.lb - into_b : c.ra - (go ? 64u : 0u);
+  c.la = step ? c.lb : c.la;
+  c.ja += step ? 1u : 0u;
+}
+
+BT_GATHER_HD void gather_step_settle(GatherStepper &st) {
+  st.c.boff = st.dsel ? st.d.off : st.c.boff;
+  st.c.lb = st.dsel ? (st.dsel == 2u ? st.d.len : 0u) : st.c.lb;
+  st.dsel = 0u;
+}
+
+// Block 0's loads.  `len` is gather_total() of the same list.
+BT_GATHER_HD void gather_step_begin(GatherStepper &st, const uint8_t *base, const GatherSeg *segs, uint32_t nseg,
+                                    uint64_t len, const uint8_t *idle) {
+  gather_begin(st.c, base, segs, nseg);
+  st.b = 0;
+  st.nfull = len >> 6;
+  st.r = (uint32_t)len & 63u;
+  st.nb = st.nfull + (st.r >= 56u ? 2u : 1u);
+  st.bits = len * 8ull;
+  const bool go = st.nfull != 0 && gather_regular(st.c);
+  gather_fetch_if(st, go, idle);
+  st.ahead = go ? 1u : 0u;
+}
+
+// w = block b as 16 big-endian words, then the loads of block b + 1.
+BT_GATHER_HD void gather_step(GatherStepper &st, uint32_t (&w)[16], const uint8_t *idle) {
+  gather_step_settle(st);
+  gather_words(w, st.s);
+  if (!st.ahead) {
+    // By bytes; behind this branch no load is in flight (the slot was waited
+    // for above), so its join costs the prefetch nothing.
+    const uint32_t want = st.b < st.nfull ? 64u : (st.b == st.nfull ? st.r : 0u);
+    gather_bytes_upto(st.c, w, want);  // zeroes w; want == 0 reads nothing
+    if (want) gather_load_b(st.c);
+    const bool tail = st.b == st.nfull, last = st.b + 1u == st.nb;
+    const uint32_t wi = st.r >> 2, mark = 0x80000000u >> ((st.r & 3u) * 8u);
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) w[j] |= tail && j == wi ? mark : 0u;
+    w[14] = last ? (uint32_t)(st.bits >> 32) : w[14];
+    w[15] = last ? (uint32_t)st.bits : w[15];
+  }
+  ++st.b;
+  const bool go = st.b < st.nfull && gather_regular(st.c);
+  gather_fetch_if(st, go, idle);
+  st.ahead = go ? 1u : 0u;
 }
 
 }  // namespace btsha1

@@ -34,6 +34,9 @@
 //   k_sha1_gather / k_sha1_gather_verify  messages given as lists of segments
 //                   (a chunk hashed where its datagrams landed), one message
 //                   per lane; the segment walk is sha1_gather_walk.h.
+//   k_sha1_gather_lat  k_sha1_lat_ragged's split for 64 segment-list messages
+//                   (off by default, bt_sha1_set_seglist_latency_batch): S steps
+//                   through each lane's list, one block per call.
 //   k_sha1_gather_resume / k_sha1_gather_resume_table  k_sha1_resume's S / R
 //                   split over a segment list that is still growing: S seeks
 //                   each block's segment (a chunk hashed while its datagrams arrive).
@@ -1507,6 +1510,126 @@ __global__ __launch_bounds__(kBlock) void k_sha1_gather_verify(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------
+// Latency form of the scatter-gather batch (btsha1_launch_gather_lat, behind
+// bt_sha1_set_seglist_latency_batch): k_sha1_lat_ragged's loader / round-wave
+// split with an S wave that walks segment lists.  Lane j of both waves owns
+// message 64*wg + j; lanes past n redo the last message and store nothing.
+//   S  sums its message's segment lengths (gather_total), then calls the
+//      stepper of sha1_gather_walk.h nbmax times in wave-uniform control flow:
+//      one block per call per lane -- regular, by bytes, padding, or zeros once
+//      the lane's message is through -- with the next block's loads in flight
+//      while produce_block runs.  No barrier sits in a lane-dependent branch.
+//   R  is k_sha1_lat_ragged's, with 64-bit block counts.
+// Trip count: only S reads the descriptors.  It publishes nb[lane] in LDS
+// before its first barrier; R reads it behind its own first barrier, so both
+// waves take nbmax = wave_max(nb) from the same 64 values and execute exactly
+// nbmax + SLOTS - 1 barriers each ("Barrier accounting" above).
+// VERIFY is a run-time choice (ok != nullptr, uniform over the grid).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+    const uint64_t u = ((uint64_t)hi << 32) | lo;
+    v = u > v ? u : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+         __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+template <int SLOTS>
+__global__ __launch_bounds__(128) void k_sha1_gather_lat(const uint8_t *__restrict__ base,
+                                                         const GatherSeg *__restrict__ segs,
+                                                         const uint64_t *__restrict__ seg_first,
+                                                         const uint32_t *__restrict__ seg_count, uint64_t n,
+                                                         uint8_t *__restrict__ digests,
+                                                         const uint8_t *__restrict__ expected,
+                                                         uint8_t *__restrict__ ok) {
+  __shared__ u32x4 lds[SLOTS][20 * 64];
+  __shared__ uint64_t nbs[64];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t idx = (uint64_t)blockIdx.x * 64u + lane;
+  uint32_t nbar = 0;
+  (void)nbar;
+  if (wave == 0) {
+    // ---- S -------------------------------------------------------------------
+    const uint64_t mi = idx < n ? idx : n - 1;
+    const GatherSeg *list = segs + seg_first[mi];
+    const uint32_t nseg = seg_count[mi];
+    const uint8_t *idle = (const uint8_t *)kZeroBlock;
+    GatherStepper st;
+    gather_step_begin(st, base, list, nseg, gather_total(list, nseg), idle);
+    nbs[lane] = st.nb;
+    const uint64_t nbmax = uniform64(wave_max64(st.nb));
+    uint32_t slot = 0;
+    for (uint64_t b = 0; b < nbmax; ++b) {
+      uint32_t w[16];
+      gather_step(st, w, idle);
+      __builtin_amdgcn_sched_barrier(0);
+      produce_block<SLOTS>(w, lds, slot, lane, nbar);
+    }
+#pragma unroll
+    for (int k = 0; k < SLOTS - 1; ++k) BT_LAT_BARRIER(nbar);  // pair with R's last barriers
+    BT_LAT_CHECK(nbar, nbmax + SLOTS - 1u);
+  } else {
+    // ---- R -------------------------------------------------------------------
+    State st, fin;
+    st.init();
+    fin = st;
+    BT_LAT_BARRIER(nbar);  // block 0 and nbs are in
+    const uint64_t nb = nbs[lane];
+    const uint64_t nbmax = uniform64(wave_max64(nb));
+    auto latch = [&](uint64_t b) {  // this lane's last block done: keep its state
+      if (b + 1u == nb) fin = st;
+    };
+    if constexpr (SLOTS == 2) {
+      for (uint64_t b = 0; b < nbmax; ++b) {
+        uint32_t a = st.h0, bb = st.h1, c = st.h2, d = st.h3, e = st.h4;
+        consume_wk<0, 80>(a, bb, c, d, e, lds[b & 1u], lane);
+        BT_LAT_BARRIER(nbar);
+        st.h0 += a;  // sha.c:446-450
+        st.h1 += bb;
+        st.h2 += c;
+        st.h3 += d;
+        st.h4 += e;
+        latch(b);
+      }
+    } else {
+      BT_LAT_BARRIER(nbar);
+      u32x4 wa[20], wb[20];
+      lat_fetch(wa, lds[0], lane);
+      uint32_t sb = 0;
+      for (uint64_t b = 0; b < nbmax; b += 2) {
+        const uint32_t s1 = sb + 1u == 3u ? 0u : sb + 1u;
+        const uint32_t s2 = s1 + 1u == 3u ? 0u : s1 + 1u;
+        lat_fetch(wb, lds[b + 1 < nbmax ? s1 : sb], lane);
+        lat_rounds(st, wa);
+        latch(b);
+        BT_LAT_BARRIER(nbar);
+        if (b + 1 < nbmax) {
+          lat_fetch(wa, lds[b + 2 < nbmax ? s2 : s1], lane);
+          lat_rounds(st, wb);
+          latch(b + 1);
+          BT_LAT_BARRIER(nbar);
+        }
+        sb = s2;
+      }
+    }
+    BT_LAT_CHECK(nbar, nbmax + SLOTS - 1u);
+    if (idx < n) {
+      if (ok) store_digest_bytes<true>(fin, idx, digests, expected, ok);
+      else store_digest_bytes<false>(fin, idx, digests, nullptr, nullptr);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Frozen synthetic generator: word g of the stream = splitmix64(seed + g),
 // stored little-endian (mirrored by oracle/sha1_oracle.c:or_fill_synthetic).
 // ---------------------------------------------------------------------------
@@ -2054,13 +2177,49 @@ hipError_t btsha1_launch_ragged_verify(const void *d_base, const uint64_t *d_off
   return hipGetLastError();
 }
 
-// One message per lane at every n (no chain or loader / round-wave form walks
-// segments yet); the workgroup width as btsha1_launch_ragged's last form.
+// Segment-list batches of at most this many messages take the latency form
+// (0, the default: never).
+static uint64_t g_seglist_lat_max = 0;
+void btsha1_set_seglist_latency_batch(uint64_t max_messages) {
+  __atomic_store_n(&g_seglist_lat_max, max_messages, __ATOMIC_RELAXED);
+}
+uint64_t btsha1_seglist_latency_batch_setting() { return __atomic_load_n(&g_seglist_lat_max, __ATOMIC_RELAXED); }
+uint64_t btsha1_seglist_latency_batch() {
+  const uint64_t v = btsha1_seglist_latency_batch_setting();
+  return v == BT_SHA1_SEGLIST_LATENCY_AUTO ? (uint64_t)btsha1_device_cus() * 128u : v;
+}
+
+const char *btsha1_seglist_kernel_name(uint64_t n) {
+  if (btsha1_seglist_latency_batch_setting() == 0 || n > btsha1_seglist_latency_batch()) return "k_sha1_gather";
+  return (n + 63) / 64 > btsha1_device_cus() ? "k_sha1_gather_lat<3>" : "k_sha1_gather_lat<2>";
+}
+
+hipError_t btsha1_launch_gather_lat(const void *base, const void *segs, const uint64_t *seg_first,
+                                    const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp,
+                                    uint8_t *ok, hipStream_t s) {
+  const uint64_t grid = n / 64 + (n % 64 ? 1 : 0);
+  if (!base || !segs || !seg_first || !seg_count || n == 0 || (ok && !exp) || (!ok && !dig) || grid > 0x7fffffffull)
+    return hipErrorInvalidValue;
+  if (grid > btsha1_device_cus())
+    hipLaunchKernelGGL(k_sha1_gather_lat<3>, dim3((uint32_t)grid), dim3(128), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_first, seg_count, n, dig, exp, ok);
+  else
+    hipLaunchKernelGGL(k_sha1_gather_lat<2>, dim3((uint32_t)grid), dim3(128), 0, s, (const uint8_t *)base,
+                       (const GatherSeg *)segs, seg_first, seg_count, n, dig, exp, ok);
+  return hipGetLastError();
+}
+
+// One message per lane (no chain form takes whole segment lists: it needs a
+// pos table); the workgroup width as btsha1_launch_ragged's last form.  Up to
+// btsha1_seglist_latency_batch() messages (off by default) take the loader /
+// round-wave form instead.
 hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64_t *seg_first,
                                 const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp, uint8_t *ok,
                                 hipStream_t s) {
   if (!base || !segs || !seg_first || !seg_count || (ok && !exp) || n > BTSHA1_GATHER_MAX) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
+  if (btsha1_seglist_latency_batch_setting() != 0 && n <= btsha1_seglist_latency_batch())
+    return btsha1_launch_gather_lat(base, segs, seg_first, seg_count, n, dig, exp, ok, s);
   const uint32_t wg = chain_workgroup(n);
   const uint64_t grid = (n + wg - 1) / wg;
   if (ok)

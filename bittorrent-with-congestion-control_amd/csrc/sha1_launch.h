@@ -108,6 +108,23 @@ BTSHA1_HIDDEN hipError_t btsha1_launch_ragged_verify(const void *d_base, const u
 BTSHA1_HIDDEN hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64_t *seg_first,
                                               const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp,
                                               uint8_t *ok, hipStream_t s);
+// Its latency form (k_sha1_gather_lat<2 / 3>: one two-wave workgroup per 64
+// messages, three LDS slots when the grid exceeds the CU count, else two, as
+// btsha1_launch_ragged chooses): the same arguments and results.
+// hipErrorInvalidValue and no launch for a null base, segs, seg_first or
+// seg_count, n == 0, ok without exp, neither ok nor dig, or a grid above
+// 2^31 - 1.
+// btsha1_launch_gather takes it for n <= btsha1_seglist_latency_batch():
+// 0 (the default) never, BT_SHA1_SEGLIST_LATENCY_AUTO 128 x CUs of the
+// launching device.
+#define BT_SHA1_SEGLIST_LATENCY_AUTO UINT64_MAX
+BTSHA1_HIDDEN hipError_t btsha1_launch_gather_lat(const void *base, const void *segs, const uint64_t *seg_first,
+                                                  const uint32_t *seg_count, uint64_t n, uint8_t *dig,
+                                                  const uint8_t *exp, uint8_t *ok, hipStream_t s);
+BTSHA1_HIDDEN void btsha1_set_seglist_latency_batch(uint64_t max_messages);
+BTSHA1_HIDDEN uint64_t btsha1_seglist_latency_batch_setting();
+BTSHA1_HIDDEN uint64_t btsha1_seglist_latency_batch();
+BTSHA1_HIDDEN const char *btsha1_seglist_kernel_name(uint64_t n);
 // The single-message form (grid 1): offset, length and total are kernel
 // arguments, so a host object launches it with no device-side arrays.
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,

@@ -80,6 +80,19 @@ uint64_t bt_sha1_set_latency_batch(uint64_t max_chunks);
  * one-message-per-lane ragged kernel.  0 disables it; UINT64_MAX (default) =
  * two per compute unit.  Returns the previous setting. */
 uint64_t bt_sha1_set_chain_batch(uint64_t max_messages);
+/* Segment-list batches (bt_sha1_gather_dev, bt_sha1_gather_verify_dev, a
+ * gather verifier's batch launch) of at most max_messages messages take the
+ * latency form k_sha1_gather_lat: a loader wave that walks the segment lists
+ * and a round wave per 64 messages, as the latency kernel above; larger
+ * batches the one-message-per-lane kernel.  0 (the default) disables it;
+ * UINT64_MAX = 128 messages per compute unit of the launching device.
+ * Returns the previous setting; needs no device. */
+uint64_t bt_sha1_set_seglist_latency_batch(uint64_t max_messages);
+/* Name of the kernel a segment-list batch of n messages runs under the
+ * current setting and device: "k_sha1_gather_lat<2>" (at most one workgroup
+ * per compute unit), "k_sha1_gather_lat<3>" or "k_sha1_gather".  Needs no
+ * device (256 compute units are assumed without one). */
+const char *bt_sha1_seglist_kernel_name(uint64_t n);
 /* Name of the kernel a fixed-layout batch of n_chunks chunks runs on the
  * current device ("k_sha1_chain" up to two chunks per CU, "k_sha1_lat" up to
  * the latency batch, else "k_sha1_fixed" -- or, in the experiments library

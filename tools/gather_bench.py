@@ -18,7 +18,10 @@ datagrams + gather hash + verdict), -z (payloads landed contiguously) and
 packetized (util.c:275's 1484-byte memcpys); -G and -z time 4 rounds over the
 resident slots after the landing round, packetized 2 rounds after 1 untimed.
 Rates are over hashed (payload) bytes.
-usage: gather_bench.py [--host-gib G] [--no-device] [N ...]
+--lat: beside each n, bt_sha1_gather_dev with the segment-list latency knob on
+(bt_sha1_set_seglist_latency_batch(auto): k_sha1_gather_lat), the launches
+interleaved with the knob-off ones in the same session, digests equal.
+usage: gather_bench.py [--host-gib G] [--no-device] [--lat] [N ...]
 """
 import argparse
 import json
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("sizes", nargs="*", type=int)
     ap.add_argument("--host-gib", type=float, default=8.0)
     ap.add_argument("--no-device", action="store_true")
+    ap.add_argument("--lat", action="store_true")
     a = ap.parse_args()
     sizes = a.sizes or [64, 4096, 32768]
     assert (NDG - 1) * PAYLOAD + LAST == CHUNK
@@ -144,6 +148,32 @@ def main():
                 lanes = statistics.median(timed(ragged) for _ in range(5))
             finally:
                 bt.set_latency_batch(before)
+        lat = {}
+        if a.lat:
+            def gather_lat():
+                before = bt.set_seglist_latency_batch(2**64 - 1)
+                try:
+                    gather()
+                finally:
+                    bt.set_seglist_latency_batch(before)
+
+            gd.zero_()
+            for _ in range(2):
+                gather_lat()
+            torch.cuda.synchronize()
+            assert torch.equal(gd, rd), n
+            to, tl = [], []
+            for _ in range(5):
+                to.append(timed(gather))
+                tl.append(timed(gather_lat))
+            before = bt.set_seglist_latency_batch(2**64 - 1)
+            name = bt.seglist_kernel_name(n)
+            bt.set_seglist_latency_batch(before)
+            mo, ml = statistics.median(to), statistics.median(tl)
+            lat = {"knob_on_kernel": name, "knob_off_median_ms": round(mo, 4), "knob_on_median_ms": round(ml, 4),
+                   "knob_on_over_off": round(ml / mo, 3), "knob_on_over_ragged": round(ml / mr, 3),
+                   "knob_on_us_per_block": round(ml * 1e3 / (CHUNK // 64 + 1), 4),
+                   "knob_off_ms": [round(x, 4) for x in to], "knob_on_ms": [round(x, 4) for x in tl]}
         blocks = CHUNK // 64 + 1
         print(json.dumps({"n": n, "payload_bytes": n * CHUNK, "wire_bytes": n * SLOT,
                           "gather_dev_median_ms": round(mg, 4), "ragged_dev_median_ms": round(mr, 4),
@@ -155,7 +185,7 @@ def main():
                           "gather_us_per_block": round(mg * 1e3 / blocks, 4),
                           "ragged_us_per_block": round(mr * 1e3 / blocks, 4),
                           "gather_dev_ms": [round(x, 4) for x in tg], "ragged_dev_ms": [round(x, 4) for x in tr],
-                          "source_id": bt.source_id()}), flush=True)
+                          **lat, "source_id": bt.source_id()}), flush=True)
         del wire, flat, dg, fv, d_seg
 
 
