@@ -38,12 +38,18 @@ HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/
 # part of what keeps the product under half the experiments library
 # (tests/test_abi.py).  The asan build keeps its symbols.
 SONAME   := -Wl,-soname,libbtsha1.so -Wl,--strip-all
+# The gfx950 code object inside keeps its static symbol table -- the HIP runtime
+# reads it (kernels, device variables), and a library whose code object had none
+# crashed at its first launch -- but not the LOCAL symbols in it: eight
+# compiler-internal resource symbols per kernel (<kernel>.num_vgpr, ...), 32 KB
+# of names that nothing looks up.  The dynamic symbols and the code are untouched.
+KSTRIP   := -Xoffload-linker --discard-all
 # One build of the library: $(call libbtsha1,object dir,library,kernel flags,
 # host flags,source id suffix,host objects besides bt_runtime.o,link flags)
 define libbtsha1
 $(1)/sha1_kernels.o: $$(KDEPS)
 	@mkdir -p $$(dir $$@)
-	$$(HIPCC) $$(HIPFLAGS) $(3) -c $$< -o $$@
+	$$(HIPCC) $$(HIPFLAGS) $$(KSTRIP) $(3) -c $$< -o $$@
 $(1)/%.o: $$(CSRC)/%.cpp $$(HDRS) $$(KDEPS)
 	@mkdir -p $$(dir $$@)
 	$$(HIPCC) $$(HIPFLAGS) $(4) -DBT_SHA1_SRC_ID='"$$(SRC_ID)$(5)"' -c $$< -o $$@

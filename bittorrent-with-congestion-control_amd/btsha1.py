@@ -123,6 +123,8 @@ class VerifierGatherStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_verifi
 
 _sig("bt_sha1_gather_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp)
 _sig("bt_sha1_gather_verify_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
+_sig("bt_sha1_set_segchain_batch", _u64, _u64)
+_sig("bt_sha1_segchain_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, ctypes.c_uint32, _vp)
 _sig("bt_sha1_verifier_create_gather", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
      ctypes.c_uint32)
 _sig("bt_sha1_verifier_commit_gather", ctypes.c_int, _vp, _vp, ctypes.POINTER(Seg), ctypes.c_uint32, _vp, _u64)
@@ -231,6 +233,12 @@ def set_seglist_latency_batch(max_messages):
     return lib.bt_sha1_set_seglist_latency_batch(max_messages)
 
 
+def set_segchain_batch(max_messages):
+    """Segment-list batches of <= max_messages take k_sha1_gather_chain, ahead of the latency
+    form (0, the default: never; 2**64 - 1: 2 per CU); returns the previous setting."""
+    return lib.bt_sha1_set_segchain_batch(max_messages)
+
+
 def seglist_kernel_name(n):
     """Kernel a segment-list batch of n messages runs under the current setting and device."""
     return lib.bt_sha1_seglist_kernel_name(n).decode()
@@ -324,6 +332,16 @@ def gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d
     """gather_dev with the fused compare, as ragged_verify_dev."""
     _check(lib.bt_sha1_gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d_ok, d_digests,
                                          stream), "bt_sha1_gather_verify_dev")
+
+
+def segchain_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected=None, d_ok=None, d_digests=None,
+                 piece_bytes=0, stream=None):
+    """One launch of k_sha1_gather_chain (diagnostic): gather_verify_dev's
+    messages and results, one two-wave workgroup per message, whatever
+    set_segchain_batch says.  d_expected and d_ok come together or not at all;
+    piece_bytes (0: the production 2**31) caps the bytes of one pass."""
+    _check(lib.bt_sha1_segchain_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d_ok, d_digests,
+                                    piece_bytes, stream), "bt_sha1_segchain_dev")
 
 
 def states_init_dev(d_states, n, stream=None):

@@ -249,6 +249,12 @@ uint64_t bt_sha1_set_seglist_latency_batch(uint64_t max_messages) {
   return prev;
 }
 
+uint64_t bt_sha1_set_segchain_batch(uint64_t max_messages) {
+  const uint64_t prev = btsha1_segchain_batch_setting();
+  btsha1_set_segchain_batch(max_messages);
+  return prev;
+}
+
 const char *bt_sha1_seglist_kernel_name(uint64_t n) { return btsha1_seglist_kernel_name(n); }
 
 const char *bt_sha1_kernel_name(uint64_t n_chunks) {
@@ -468,6 +474,46 @@ int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, con
                               const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
                               uint8_t *d_digests, void *stream) {
   return gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, d_expected, d_ok, true, stream);
+}
+
+// Diagnostic, like bt_sha1_column_dev: ONE launch of the chain form of the
+// segment-list kernels whatever bt_sha1_set_segchain_batch says.  What the
+// launcher would refuse is refused here with a message, before any device call.
+int bt_sha1_segchain_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                         const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
+                         uint8_t *d_digests, uint32_t piece_bytes, void *stream) {
+  if (n == 0) return 0;
+  if (!d_base || !d_segs || !d_seg_first || !d_seg_count) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (!d_expected != !d_ok) {
+    set_err("segchain: d_expected and d_ok come together or not at all");
+    return -1;
+  }
+  if (!d_ok && !d_digests) {
+    set_err("segchain: neither d_digests nor d_ok: nothing to write");
+    return -1;
+  }
+  const uint32_t piece = piece_bytes ? piece_bytes : BTSHA1_SEGCHAIN_PIECE;
+  if ((piece & 63u) || piece > BTSHA1_SEGCHAIN_PIECE) {
+    set_err("segchain: piece_bytes %u must be 0 or a 64-byte multiple of at most %u", piece_bytes,
+            BTSHA1_SEGCHAIN_PIECE);
+    return -1;
+  }
+  if (n > BTSHA1_RESUME_MAX) {  // one workgroup per message
+    set_err("segchain: %llu messages exceed the grid limit of %llu per launch", (unsigned long long)n,
+            (unsigned long long)BTSHA1_RESUME_MAX);
+    return -1;
+  }
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  DevCtx *c = ctx_for(dev);
+  if (!c) return -1;
+  hipStream_t st = pick_stream(stream);
+  BT_CK(btsha1_launch_gather_chain(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, d_expected, d_ok, piece,
+                                   st));
+  return 0;
 }
 
 int bt_sha1_states_init_dev(uint32_t *d_states, uint64_t n, void *stream) {

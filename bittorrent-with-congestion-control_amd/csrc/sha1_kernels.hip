@@ -40,6 +40,10 @@
 //   k_sha1_gather_resume / k_sha1_gather_resume_table  k_sha1_resume's S / R
 //                   split over a segment list that is still growing: S seeks
 //                   each block's segment (a chunk hashed while its datagrams arrive).
+//   k_sha1_gather_chain  the same body over a WHOLE segment list with
+//                   k_sha1_gather's arguments (off by default,
+//                   bt_sha1_set_segchain_batch): wave 0 builds the position
+//                   table window by window in LDS.
 //   k_fill_synthetic  frozen counter-based generator (bench/test data in HBM).
 //   k_lookup_build / k_lookup_query  digest -> first index table in HBM
 //                   (get_chunk_id / find_chunk, util.c:3-39).
@@ -1894,6 +1898,203 @@ __global__ __launch_bounds__(128) void k_sha1_gather_resume_table(const BtSha1Ga
                              reinterpret_cast<uint32_t *>(cb + 88), ent.seq);
 }
 
+// ---------------------------------------------------------------------------
+// Chain form for whole segment lists (bt_sha1_segchain_dev; btsha1_launch_gather
+// behind bt_sha1_set_segchain_batch): k_sha1_gather's arguments, one two-wave
+// workgroup per message, gather_resume_body<true> unchanged (one instantiation:
+// without `ok` its compare is pointed at LDS).  The body wants a pos
+// table beside the descriptors; this kernel has none, so wave 0 builds one for
+// a WINDOW of the list in LDS and the body runs over that window -- through
+// generic pointers: the S wave's descriptor and pos reads become flat loads
+// that land in LDS, and gather_span_at and the body compile from the very text
+// the resume kernels use (no scratch copy in global memory is needed).
+//
+// The workgroup walks its message window by window.  Wave 0 keeps
+//   k     the list entry at which the next window starts: the first segment
+//         that still has unhashed bytes, or an empty one before it
+//   skip  bytes of the window's first kept segment that are hashed already
+//   done  bytes hashed so far (a 64-byte multiple)
+// and each trip of the loop
+//   builds  reads descriptors from list[k ..] 64 per step (none at or past
+//           seg_count), keeps the next up to 1024 NON-EMPTY ones (ballot +
+//           prefix count; empty segments are dropped) with their running byte
+//           positions relative to the first kept one (wave prefix sum) -- 16 KiB
+//           + 8 KiB of LDS; a kept descriptor's `reserved` word carries its
+//           list index.  Then the summary: A = the window's bytes - skip,
+//           whether the list ended inside the window, and from them the piece;
+//   barrier both waves, then both read the summary;
+//   hashes  a FINISH when the list ended and A <= piece: the body with
+//           from = skip, len = A, total = done + A; else an ADVANCE over
+//           len = min(A, piece) & ~63 bytes (total = 0).  A window that is not
+//           the list's last holds 1024 non-empty segments, so A >= 1024 and an
+//           advance always moves;
+//   slides  (wave 0, after an advance) to the kept segment that holds window
+//           byte skip + len -- a ballot count over pos[] -- or to the entry
+//           behind the window when the piece ended with it.
+// The chaining state lives in LDS (five words, the IV at first); the body
+// reads and writes it through st_io like a resume kernel's state array.
+// A message of no bytes (seg_count 0 or every length 0) never reaches the
+// body: lane 0 of wave 1 writes the digest of the empty string.
+// `piece` (a 64-byte multiple, at most 2^31: the body's len is 32 bits) caps
+// one body call; the launcher passes 2^31, tests pass 64 to put a piece
+// boundary inside every window.
+// Barriers: all control flow above is workgroup-uniform (the summary is read
+// behind the window's barrier).  With T windows built and the body called for
+// windows t < T' (T' = T, or 0 for the empty message, where T = 1), BOTH waves
+// execute
+//     T + sum over t < T' of (nbatch_t + 1)
+// barriers, nbatch_t = ceil(nb_t / 64), nb_t = len_t >> 6 for an advance and
+// (len_t >> 6) + ((len_t & 63) >= 56 ? 2 : 1) for the finish.  The body checks
+// its own nbatch_t + 1 per call, this kernel its T window barriers.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kGatherWindow = 1024;
+
+__device__ __forceinline__ uint64_t wave_scan_incl(uint64_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d += d) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
+    v += lane >= d ? ((uint64_t)hi << 32) | lo : 0ull;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(128) void k_sha1_gather_chain(const uint8_t *__restrict__ base,
+                                                           const GatherSeg *__restrict__ segs,
+                                                           const uint64_t *__restrict__ seg_first,
+                                                           const uint32_t *__restrict__ seg_count, uint64_t n,
+                                                           uint8_t *__restrict__ dig, const uint8_t *__restrict__ exp,
+                                                           uint8_t *__restrict__ ok, uint32_t piece) {
+  __shared__ u32x4 lds[2][kChainStride * kChainBatch];  // as k_sha1_chain: 2 slots x 64 blocks, 42 KiB
+  __shared__ alignas(16) GatherSeg wseg[kGatherWindow];  // the window: kept descriptors, 16 KiB
+  __shared__ uint64_t wpos[kGatherWindow];               // and their positions, 8 KiB
+  __shared__ uint64_t s_total;
+  __shared__ uint32_t s_state[5], s_nseg, s_from, s_len, s_mode;
+  __shared__ uint8_t s_ok;  // where the fused compare's verdict goes when nobody asked for it
+  const uint64_t i = blockIdx.x;
+  if (i >= n) return;  // the whole workgroup, before any barrier
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const GatherSeg *list = segs + seg_first[i];
+  const uint32_t count = seg_count[i];
+  uint8_t *digp = dig ? dig + 20 * i : nullptr;
+  // One instantiation serves both: without `ok` the body's compare reads 20
+  // bytes of LDS (the state) and writes its verdict to s_ok.
+  const uint8_t *expp = ok ? exp + 20 * i : reinterpret_cast<const uint8_t *>(s_state);
+  uint8_t *okp = ok ? ok + i : &s_ok;
+  enum : uint32_t { kAdvance = 0, kFinish = 1, kEmpty = 2 };
+  // Wave 0's walk state; wave 1 learns what it needs from the summary.
+  uint32_t k = 0, skip = 0, kept = 0, used = 0;
+  uint64_t done = 0, bytes = 0;
+  uint32_t wbar = 0, nwin = 0;
+  (void)wbar;
+  for (;;) {
+    if (wave == 0) {
+      if (nwin == 0 && lane < 5u) {
+        const uint32_t iv[5] = {0x67452301u, 0xEFCDAB89u, 0x98BADCFEu, 0x10325476u, 0xC3D2E1F0u};  // sha.c:149-163
+        uint32_t v = iv[0];
+#pragma unroll
+        for (uint32_t j = 1; j < 5u; ++j) v = lane == j ? iv[j] : v;
+        s_state[lane] = v;
+      }
+      // ---- build the window that starts at list[k] ---------------------------
+      kept = 0;
+      used = 0;
+      bytes = 0;
+      while (kept < kGatherWindow && (uint64_t)k + used < count) {
+        const uint64_t idx = (uint64_t)k + used + lane;
+        const bool valid = idx < count;
+        GatherSeg d;
+        d.off = 0;
+        d.len = 0;
+        if (valid) d = gather_seg(list + idx);
+        const uint32_t len = valid ? d.len : 0u;
+        const uint64_t nzmask = __ballot(len != 0u);
+        const uint32_t rank = (uint32_t)__popcll(nzmask & ((1ull << lane) - 1ull));
+        const uint32_t room = kGatherWindow - kept;
+        const bool keep = len != 0u && rank < room;
+        const uint64_t incl = wave_scan_incl(keep ? (uint64_t)len : 0ull, lane);
+        if (keep) {
+          GatherSeg w;
+          w.off = d.off;
+          w.len = len;
+          w.reserved = (uint32_t)idx;  // its list index, for the slide
+          wseg[kept + rank] = w;
+          wpos[kept + rank] = bytes + incl - len;
+        }
+        const uint32_t nz = (uint32_t)__popcll(nzmask);
+        if (nz >= room) {  // full: consumed through the last kept entry
+          const uint64_t last = __ballot(keep && rank == room - 1u);
+          used += (uint32_t)__builtin_ctzll(last) + 1u;
+          kept = kGatherWindow;
+        } else {
+          const uint64_t left = (uint64_t)count - k - used;
+          used += left < 64u ? (uint32_t)left : 64u;
+          kept += nz;
+        }
+        const uint32_t tlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)incl, 63);
+        const uint32_t thi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(incl >> 32), 63);
+        bytes += ((uint64_t)thi << 32) | tlo;
+      }
+      // ---- the piece -----------------------------------------------------------
+      const bool end = (uint64_t)k + used == count;
+      const uint64_t A = bytes - skip;
+      if (lane == 0) {
+        const bool fin = end && A <= piece;
+        s_nseg = kept;
+        s_from = skip;
+        s_len = fin ? (uint32_t)A : (uint32_t)(A < piece ? A : piece) & ~63u;
+        s_total = fin ? done + A : 0ull;
+        s_mode = fin ? (done + A == 0 ? kEmpty : kFinish) : kAdvance;
+      }
+    }
+    ++nwin;
+    BT_LAT_BARRIER(wbar);  // the window and its summary are in
+    const uint32_t mode = __builtin_amdgcn_readfirstlane(s_mode);
+    const uint32_t nseg = __builtin_amdgcn_readfirstlane(s_nseg);
+    const uint32_t from = __builtin_amdgcn_readfirstlane(s_from);
+    const uint32_t len = __builtin_amdgcn_readfirstlane(s_len);
+    const uint64_t tot = s_total;
+    const uint64_t total = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(tot >> 32)) << 32) |
+                           __builtin_amdgcn_readfirstlane((uint32_t)tot);
+    if (mode == kEmpty) {
+      if (threadIdx.x == 64u) {
+        const uint32_t h[5] = {0xda39a3eeu, 0x5e6b4b0du, 0x3255bfefu, 0x95601890u, 0xafd80709u};  // SHA-1("")
+        if (digp) {
+#pragma unroll
+          for (int j = 0; j < 20; ++j) digp[j] = (uint8_t)(h[j >> 2] >> (24 - 8 * (j & 3)));
+        }
+        // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+        uint32_t diff = 0;
+#pragma unroll
+        for (int j = 0; j < 20; ++j) diff |= (uint32_t)expp[j] ^ ((h[j >> 2] >> (24 - 8 * (j & 3))) & 0xFFu);
+        *okp = diff == 0;
+      }
+      break;
+    }
+    gather_resume_body<true>(lds, base, wseg, wpos, nseg, 0u, from, len, total, s_state, digp, expp, okp, nullptr, 0u);
+    if (mode == kFinish) break;
+    if (wave == 0) {
+      // ---- slide: the kept segment that holds window byte skip + len -----------
+      const uint64_t t = (uint64_t)skip + len;
+      done += len;
+      if (t == bytes) {  // the piece ended with the window
+        k += used;
+        skip = 0;
+      } else {
+        uint32_t c = 0;
+        for (uint32_t j0 = 0; j0 < kept; j0 += 64u) {
+          const uint32_t j = j0 + lane;
+          c += (uint32_t)__popcll(__ballot(j < kept && wpos[j < kept ? j : 0u] <= t));
+        }
+        k = __builtin_amdgcn_readfirstlane(wseg[c - 1u].reserved);
+        skip = __builtin_amdgcn_readfirstlane((uint32_t)(t - wpos[c - 1u]));
+      }
+    }
+  }
+  BT_LAT_CHECK(wbar, nwin);
+}
+
 }  // namespace btsha1
 
 // ---------------------------------------------------------------------------
@@ -2189,7 +2390,20 @@ uint64_t btsha1_seglist_latency_batch() {
   return v == BT_SHA1_SEGLIST_LATENCY_AUTO ? (uint64_t)btsha1_device_cus() * 128u : v;
 }
 
+// Segment-list batches of at most this many messages take the chain form
+// (k_sha1_gather_chain, one two-wave workgroup per message; 0, the default:
+// never; BT_SHA1_SEGCHAIN_AUTO: two per CU, as btsha1_chain_batch).  Asked
+// before the latency form.
+static uint64_t g_segchain_max = 0;
+void btsha1_set_segchain_batch(uint64_t max_messages) { __atomic_store_n(&g_segchain_max, max_messages, __ATOMIC_RELAXED); }
+uint64_t btsha1_segchain_batch_setting() { return __atomic_load_n(&g_segchain_max, __ATOMIC_RELAXED); }
+uint64_t btsha1_segchain_batch() {
+  const uint64_t v = btsha1_segchain_batch_setting();
+  return v == BT_SHA1_SEGCHAIN_AUTO ? 2ull * btsha1_device_cus() : v;
+}
+
 const char *btsha1_seglist_kernel_name(uint64_t n) {
+  if (btsha1_segchain_batch_setting() != 0 && n <= btsha1_segchain_batch()) return "k_sha1_gather_chain";
   if (btsha1_seglist_latency_batch_setting() == 0 || n > btsha1_seglist_latency_batch()) return "k_sha1_gather";
   return (n + 63) / 64 > btsha1_device_cus() ? "k_sha1_gather_lat<3>" : "k_sha1_gather_lat<2>";
 }
@@ -2209,15 +2423,29 @@ hipError_t btsha1_launch_gather_lat(const void *base, const void *segs, const ui
   return hipGetLastError();
 }
 
-// One message per lane (no chain form takes whole segment lists: it needs a
-// pos table); the workgroup width as btsha1_launch_ragged's last form.  Up to
-// btsha1_seglist_latency_batch() messages (off by default) take the loader /
-// round-wave form instead.
+hipError_t btsha1_launch_gather_chain(const void *base, const void *segs, const uint64_t *seg_first,
+                                      const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp,
+                                      uint8_t *ok, uint32_t piece, hipStream_t s) {
+  if (!base || !segs || !seg_first || !seg_count || n == 0 || (ok && !exp) || (!ok && !dig) || piece == 0 ||
+      (piece & 63u) || piece > BTSHA1_SEGCHAIN_PIECE || n > BTSHA1_RESUME_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sha1_gather_chain, dim3((uint32_t)n), dim3(128), 0, s, (const uint8_t *)base,
+                     (const GatherSeg *)segs, seg_first, seg_count, n, dig, exp, ok, piece);
+  return hipGetLastError();
+}
+
+// One message per lane; the workgroup width as btsha1_launch_ragged's last
+// form.  Up to btsha1_segchain_batch() messages (off by default) take the
+// chain form, k_sha1_gather_chain, which builds the pos table it needs window
+// by window; then up to btsha1_seglist_latency_batch() messages (off by
+// default) the loader / round-wave form.
 hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64_t *seg_first,
                                 const uint32_t *seg_count, uint64_t n, uint8_t *dig, const uint8_t *exp, uint8_t *ok,
                                 hipStream_t s) {
   if (!base || !segs || !seg_first || !seg_count || (ok && !exp) || n > BTSHA1_GATHER_MAX) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
+  if (btsha1_segchain_batch_setting() != 0 && n <= btsha1_segchain_batch())
+    return btsha1_launch_gather_chain(base, segs, seg_first, seg_count, n, dig, exp, ok, BTSHA1_SEGCHAIN_PIECE, s);
   if (btsha1_seglist_latency_batch_setting() != 0 && n <= btsha1_seglist_latency_batch())
     return btsha1_launch_gather_lat(base, segs, seg_first, seg_count, n, dig, exp, ok, s);
   const uint32_t wg = chain_workgroup(n);

@@ -125,6 +125,25 @@ BTSHA1_HIDDEN void btsha1_set_seglist_latency_batch(uint64_t max_messages);
 BTSHA1_HIDDEN uint64_t btsha1_seglist_latency_batch_setting();
 BTSHA1_HIDDEN uint64_t btsha1_seglist_latency_batch();
 BTSHA1_HIDDEN const char *btsha1_seglist_kernel_name(uint64_t n);
+// Its chain form (k_sha1_gather_chain: one two-wave workgroup per
+// message, which builds the position table of the resumable form itself, a
+// window of 1024 non-empty segments at a time in LDS): the same arguments and
+// results.  `piece` caps the bytes of one pass over a window: a 64-byte
+// multiple, at most BTSHA1_SEGCHAIN_PIECE, which is what production passes;
+// the result does not depend on it.  hipErrorInvalidValue and no launch for a
+// null base, segs, seg_first or seg_count, n == 0, ok without exp, neither ok
+// nor dig, such a piece, or n above BTSHA1_RESUME_MAX (the grid).
+// btsha1_launch_gather takes it, before the latency form, for
+// n <= btsha1_segchain_batch(): 0 (the default) never, BT_SHA1_SEGCHAIN_AUTO
+// 2 x CUs of the launching device (256 CUs where there is none).
+#define BT_SHA1_SEGCHAIN_AUTO UINT64_MAX
+#define BTSHA1_SEGCHAIN_PIECE (1u << 31)
+BTSHA1_HIDDEN hipError_t btsha1_launch_gather_chain(const void *base, const void *segs, const uint64_t *seg_first,
+                                                    const uint32_t *seg_count, uint64_t n, uint8_t *dig,
+                                                    const uint8_t *exp, uint8_t *ok, uint32_t piece, hipStream_t s);
+BTSHA1_HIDDEN void btsha1_set_segchain_batch(uint64_t max_messages);
+BTSHA1_HIDDEN uint64_t btsha1_segchain_batch_setting();
+BTSHA1_HIDDEN uint64_t btsha1_segchain_batch();
 // The single-message form (grid 1): offset, length and total are kernel
 // arguments, so a host object launches it with no device-side arrays.
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,

@@ -3,7 +3,7 @@
  * driven through the batched GPU verifier, end to end from host memory.
  *
  *   verify-stream [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every]
- *                 [-g verifiers] [-t] [-x] [-z | -G] <data-file> <chunks-file>
+ *                 [-g verifiers] [-t] [-x] [-z | -G [-c]] <data-file> <chunks-file>
  *
  * For every chunk listed in <chunks-file> ("<id> <hex>" lines, as
  * parse_has_get_chunk_file reads them, util.c:90-93) the chunk's bytes are
@@ -36,7 +36,11 @@
  * commit reads the headers, lists the payloads by sequence number (the
  * duplicate is not listed) and bt_sha1_verifier_commit_gather hashes them in
  * place.  Rounds work as with -z; the timed rate is table build + H2D + gather
- * hash + verdict, over hashed (payload) bytes.
+ * hash + verdict, over hashed (payload) bytes.  -c (with -G only) turns
+ * bt_sha1_set_segchain_batch to its auto setting before the verifiers are
+ * created: batches of at most two chunks per compute unit (-b) are then hashed
+ * by the chain form k_sha1_gather_chain, one workgroup per chunk, instead of
+ * the one-chunk-per-lane kernel; the summary then ends in "segchain": true.
  * The last line is a JSON summary with the host->verdict rate of the timed
  * rounds.
  *
@@ -316,13 +320,13 @@ static void *lane_thread(void *arg) {
 }
 
 #define USAGE \
-  "usage: %s [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every] [-g verifiers] [-t] [-x] [-z | -G] " \
+  "usage: %s [-b batch] [-s streams] [-r rounds] [-w warmup-rounds] [-p poll-every] [-g verifiers] [-t] [-x] [-z | -G [-c]] " \
   "<data-file> <chunks-file>\n"
 
 int main(int argc, char **argv) {
   int batch = 64, streams = 2, rounds = 1, corrupt = 0, zcopy = 0, poll_every = 1, G = 1, threads = 0, warm = 0, opt;
-  int gather = 0;
-  while ((opt = getopt(argc, argv, "b:s:r:w:p:g:txzG")) != -1) {
+  int gather = 0, segchain = 0;
+  while ((opt = getopt(argc, argv, "b:s:r:w:p:g:txzGc")) != -1) {
     if (opt == 'b') batch = atoi(optarg);
     else if (opt == 's') streams = atoi(optarg);
     else if (opt == 'r') rounds = atoi(optarg);
@@ -330,6 +334,7 @@ int main(int argc, char **argv) {
     else if (opt == 'x') corrupt = 1;
     else if (opt == 'z') zcopy = 1;
     else if (opt == 'G') gather = 1;
+    else if (opt == 'c') segchain = 1;
     else if (opt == 't') threads = 1;
     else if (opt == 'p') poll_every = atoi(optarg) > 0 ? atoi(optarg) : 1;
     else if (opt == 'g') G = atoi(optarg);
@@ -340,6 +345,10 @@ int main(int argc, char **argv) {
   }
   if (gather && zcopy) {
     fprintf(stderr, "verify-stream: -z and -G are two receive models, take one\n");
+    return 255;
+  }
+  if (segchain && !gather) {
+    fprintf(stderr, "verify-stream: -c selects the kernel of -G's segment lists, it needs -G\n");
     return 255;
   }
   const int resident = zcopy || gather; /* round 0 lands the data, later rounds re-commit it */
@@ -409,6 +418,7 @@ int main(int argc, char **argv) {
   struct shared sh = {img, ids, exp, clen, corrupt, resident, gather, poll_every, rounds, warm,
                       (long)batch * (streams < 2 ? 2 : streams), &bar, &t0};
   struct lane *L = calloc((size_t)G, sizeof *L);
+  if (segchain) bt_sha1_set_segchain_batch(UINT64_MAX); /* auto: up to two chunks per compute unit */
   long per_round_max = 0;
   for (int g = 0; g < G; g++) {
     L[g].sh = &sh;
@@ -495,6 +505,7 @@ int main(int argc, char **argv) {
   if (gather) /* of the timed rounds, like the rate */
     printf(", \"segments\": %ld, \"hashed_bytes\": %llu, \"wire_bytes\": %llu", segments,
            (unsigned long long)timed_bytes, (unsigned long long)wire_bytes);
+  if (segchain) printf(", \"segchain\": true");
   printf("}\n");
   return bad && !corrupt ? 1 : 0;
 }

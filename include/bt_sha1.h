@@ -88,10 +88,19 @@ uint64_t bt_sha1_set_chain_batch(uint64_t max_messages);
  * UINT64_MAX = 128 messages per compute unit of the launching device.
  * Returns the previous setting; needs no device. */
 uint64_t bt_sha1_set_seglist_latency_batch(uint64_t max_messages);
+/* The same batches of at most max_messages messages take the CHAIN form
+ * k_sha1_gather_chain instead: one two-wave workgroup per message, the lowest
+ * latency for the handful of chunks a peer has in flight (max_conn).  It is
+ * asked before the latency form above.  0 (the default) disables it;
+ * UINT64_MAX = two messages per compute unit of the launching device, as
+ * bt_sha1_set_chain_batch's default.  Returns the previous setting; needs no
+ * device. */
+uint64_t bt_sha1_set_segchain_batch(uint64_t max_messages);
 /* Name of the kernel a segment-list batch of n messages runs under the
- * current setting and device: "k_sha1_gather_lat<2>" (at most one workgroup
- * per compute unit), "k_sha1_gather_lat<3>" or "k_sha1_gather".  Needs no
- * device (256 compute units are assumed without one). */
+ * current settings and device: "k_sha1_gather_chain", "k_sha1_gather_lat<2>"
+ * (at most one workgroup per compute unit), "k_sha1_gather_lat<3>" or
+ * "k_sha1_gather".  Needs no device (256 compute units are assumed without
+ * one). */
 const char *bt_sha1_seglist_kernel_name(uint64_t n);
 /* Name of the kernel a fixed-layout batch of n_chunks chunks runs on the
  * current device ("k_sha1_chain" up to two chunks per CU, "k_sha1_lat" up to
@@ -192,6 +201,22 @@ int bt_sha1_gather_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint
 int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
                               const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected,
                               uint8_t *d_ok, uint8_t *d_digests /* may be NULL */, void *stream);
+/* Diagnostic, like bt_sha1_column_dev: ONE launch of the segment-list
+ * kernels' chain form (k_sha1_gather_chain: one two-wave workgroup per
+ * message, which needs no position table -- it builds one in LDS, a window of
+ * 1024 non-empty segments at a time) whatever bt_sha1_set_segchain_batch
+ * says.  Messages, tables and results as bt_sha1_gather_verify_dev's;
+ * d_expected and d_ok come together or not at all (without them: digests
+ * only), d_digests may be NULL with them.  piece_bytes caps the bytes hashed
+ * per pass over a window: 0 is the production value (2^31), a test passes a
+ * small 64-byte multiple to put piece boundaries inside its messages; the
+ * results do not depend on it.  n == 0 is no work; a null d_base / d_segs /
+ * d_seg_first / d_seg_count, one of d_expected / d_ok without the other,
+ * neither d_ok nor d_digests, a piece_bytes that is no 64-byte multiple or
+ * above 2^31, or n above 2^31 - 1 (the grid) are -1 before any device call. */
+int bt_sha1_segchain_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
+                         const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
+                         uint8_t *d_digests, uint32_t piece_bytes, void *stream);
 /* Resumable hashing of messages that are still arriving (a peer appends a
  * chunk's payloads in order, util.c:275, and hashes it only when complete,
  * util.c:311-313; SHA-1 resumes at every 64-byte boundary).  This is the

@@ -21,7 +21,14 @@ Rates are over hashed (payload) bytes.
 --lat: beside each n, bt_sha1_gather_dev with the segment-list latency knob on
 (bt_sha1_set_seglist_latency_batch(auto): k_sha1_gather_lat), the launches
 interleaved with the knob-off ones in the same session, digests equal.
-usage: gather_bench.py [--host-gib G] [--no-device] [--lat] [N ...]
+--chain: a leg of its own, nothing else runs.  For n = 1, 4, 64 and 2, 3, 4, 8
+x CUs chunks (or the N given) as 354 datagrams in a shuffled arrival order:
+bt_sha1_gather_verify_dev with both segment-list knobs off (what is launched by
+default), with the latency knob on, and with bt_sha1_set_segchain_batch(n)
+(k_sha1_gather_chain, also past the 2 x CUs its auto setting stops at), beside
+bt_sha1_ragged_verify_dev over the same bytes laid out contiguously; the four
+alternate inside each of 7 repetitions, verdicts checked every time.
+usage: gather_bench.py [--host-gib G] [--no-device] [--lat] [--chain] [N ...]
 """
 import argparse
 import json
@@ -79,6 +86,87 @@ def host_paths(torch, bt, gib):
               flush=True)
 
 
+def chain_leg(torch, bt, sizes, reps=7):
+    """One JSON line per n: the same n chunks as 354 datagrams in a shuffled
+    arrival order, verified (bt_sha1_gather_verify_dev) with the segment-list
+    knobs off (k_sha1_gather_verify, what is launched by default), with the
+    latency knob on (k_sha1_gather_lat) and with the chain knob on
+    (k_sha1_gather_chain), beside the same bytes contiguous through
+    bt_sha1_ragged_verify_dev.  The four launches alternate inside every
+    repetition; 2 warm-ups, HIP events, the median of `reps`."""
+    auto, cus = 2**64 - 1, torch.cuda.get_device_properties(0).multi_processor_count
+    for n in sizes or [1, 4, 64, 2 * cus, 3 * cus, 4 * cus, 8 * cus]:
+        rng = np.random.default_rng(0x5E6C + n)
+        wire = torch.empty(n * SLOT + 16, dtype=torch.uint8, device="cuda")
+        bt.fill_synthetic(wire.data_ptr(), (n * SLOT) & ~15, 0, 0x6A7E)
+        where = np.stack([rng.permutation(NDG) for _ in range(n)]).astype(np.uint64)  # where[i, seq]: arrival place
+        seg = np.zeros((n, NDG, 2), dtype=np.uint64)
+        seg[:, :, 0] = np.arange(n, dtype=np.uint64)[:, None] * SLOT + where * DGRAM + HEADER
+        seg[:, :, 1] = PAYLOAD
+        seg[:, NDG - 1, 1] = LAST
+        idx = torch.from_numpy(where.astype(np.int64)).cuda()
+        dg = wire[:n * SLOT].view(n, NDG, DGRAM)
+        by_seq = torch.gather(dg, 1, idx[:, :, None].expand(n, NDG, DGRAM))
+        flat = torch.empty(n * CHUNK, dtype=torch.uint8, device="cuda")
+        fv = flat.view(n, CHUNK)
+        fv[:, :(NDG - 1) * PAYLOAD] = by_seq[:, :NDG - 1, HEADER:].reshape(n, -1)
+        fv[:, (NDG - 1) * PAYLOAD:] = by_seq[:, NDG - 1, HEADER:HEADER + LAST]
+        del by_seq, idx
+        d_seg = torch.from_numpy(seg.view(np.uint8).reshape(-1)).cuda()
+        d_first = torch.arange(n, dtype=torch.int64, device="cuda") * NDG
+        d_count = torch.full((n,), NDG, dtype=torch.int32, device="cuda")
+        d_off = torch.arange(n, dtype=torch.int64, device="cuda") * CHUNK
+        d_len = torch.full((n,), CHUNK, dtype=torch.int32, device="cuda")
+        exp = torch.zeros(20 * n, dtype=torch.uint8, device="cuda")
+        bt.ragged_dev(flat.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, exp.data_ptr())
+        torch.cuda.synchronize()
+        exp[20 * (n - 1) + 7] ^= 4  # one chunk fails: a verdict of all ones proves nothing
+        want = torch.ones(n, dtype=torch.uint8, device="cuda")
+        want[n - 1] = 0
+        ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+        def seglist(chain, lat):
+            def run():
+                c, l = bt.set_segchain_batch(chain), bt.set_seglist_latency_batch(lat)
+                try:
+                    bt.gather_verify_dev(wire.data_ptr(), d_seg.data_ptr(), d_first.data_ptr(), d_count.data_ptr(), n,
+                                         exp.data_ptr(), ok.data_ptr())
+                    return bt.seglist_kernel_name(n)
+                finally:
+                    bt.set_segchain_batch(c)
+                    bt.set_seglist_latency_batch(l)
+            return run
+
+        def contiguous():
+            bt.ragged_verify_dev(flat.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, exp.data_ptr(), ok.data_ptr())
+            return "bt_sha1_ragged_verify_dev"
+
+        legs = {"off": seglist(0, 0), "lat": seglist(0, auto), "chain": seglist(n, 0), "contiguous": contiguous}
+        names, times = {}, {k: [] for k in legs}
+        for rep in range(2 + reps):
+            for k, fn in legs.items():
+                ok.zero_()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                names[k] = fn()
+                b.record()
+                b.synchronize()
+                assert torch.equal(ok, want), (n, k)
+                if rep >= 2:
+                    times[k].append(a.elapsed_time(b))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        print(json.dumps({"leg": "chain", "n": n, "cus": cus, "kernels": names,
+                          "off_median_ms": round(med["off"], 4), "lat_median_ms": round(med["lat"], 4),
+                          "chain_median_ms": round(med["chain"], 4), "contiguous_median_ms": round(med["contiguous"], 4),
+                          "chain_over_off": round(med["chain"] / med["off"], 3),
+                          "chain_over_lat": round(med["chain"] / med["lat"], 3),
+                          "chain_over_contiguous": round(med["chain"] / med["contiguous"], 3),
+                          "chain_us_per_block": round(med["chain"] * 1e3 / (CHUNK // 64 + 1), 4),
+                          "ms": {k: [round(x, 4) for x in v] for k, v in times.items()},
+                          "auto_would_route": n <= 2 * cus, "source_id": bt.source_id()}), flush=True)
+        del wire, flat, dg, fv, d_seg
+
+
 def main():
     import torch
     import btsha1 as bt
@@ -87,9 +175,13 @@ def main():
     ap.add_argument("--host-gib", type=float, default=8.0)
     ap.add_argument("--no-device", action="store_true")
     ap.add_argument("--lat", action="store_true")
+    ap.add_argument("--chain", action="store_true")
     a = ap.parse_args()
     sizes = a.sizes or [64, 4096, 32768]
     assert (NDG - 1) * PAYLOAD + LAST == CHUNK
+    if a.chain:  # a leg of its own: the knobs off and on over the same batches, nothing else
+        chain_leg(torch, bt, a.sizes)
+        return
     if a.host_gib > 0:
         host_paths(torch, bt, a.host_gib)
     for n in [] if a.no_device else sizes:
