@@ -11,7 +11,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Iinclude -I$(CSRC
 # includes), so a comment-only edit keeps the id and the profiles tied to it.
 # Any gcc failure or an empty result falls back to hashing the raw files
 # (prefix "raw-"), so a broken strip can never alias every build to one id.
-KSRC     := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_gather_walk.h
+KSRC     := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_gather_walk.h $(CSRC)/sha1_pkt_walk.h
 SRC_ID   := $(shell out=$$(for f in $(KSRC); do gcc -fpreprocessed -dD -E -P -x c++ $$f 2>/dev/null || exit 1; done) \
               && [ -n "$$out" ] && printf '%s\n' "$$out" | sha256sum | cut -c1-16)
 ifeq ($(strip $(SRC_ID)),)
@@ -31,7 +31,7 @@ lib: $(LIB)
 # variant but asan (which instruments all host code) links the product's.
 HOST     := bt_hostmem bt_columns bt_pipeline bt_dropin bt_verifier bt_receiver bt_intake bt_chunks
 HOSTOBJ  := $(HOST:%=$(PKG)/build/%.o)
-KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/sha1_gather_walk.h
+KDEPS    := $(CSRC)/sha1_kernels.hip $(CSRC)/sha1_device.h $(CSRC)/sha1_launch.h $(CSRC)/sha1_gather_walk.h $(CSRC)/sha1_pkt_walk.h
 HDRS     := $(CSRC)/bt_runtime.h $(CSRC)/bt_columns.h include/bt_sha1.h include/sha.h include/chunk.h
 # The shipped builds carry no static symbol table (--strip-all: .dynsym stays,
 # the kernels' own symbols live inside the code object): 42 KB less in each,
@@ -142,6 +142,15 @@ $(STEPDIR)/gather_step_check: tests/native/gather_step_check.cpp $(CSRC)/sha1_ga
 	@mkdir -p $(STEPDIR)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
 
+# The same for the walk of k_sha1_pkts (sha1_pkt_walk.h): slot and order
+# array allocated exactly, every fetched address recorded;
+# tests/test_pkt_walk_host.py builds and runs it too.
+PKTDIR   := build_variants/pkt_walk
+pkt_walk_check: $(PKTDIR)/pkt_walk_check
+$(PKTDIR)/pkt_walk_check: tests/native/pkt_walk_check.cpp $(CSRC)/sha1_pkt_walk.h
+	@mkdir -p $(PKTDIR)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$(CSRC) -o $@ $<
+
 # Barrier-accounting build: the latency / chain / ragged-latency kernels count
 # the s_barriers each wave executes and check them against the invariant they
 # rely on (sha1_kernels.hip, "Barrier accounting"); bt_sha1_debug_barrier_stats
@@ -199,4 +208,4 @@ clean:
 	rm -rf $(PKG)/build $(LIB) $(BIN)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check gather_seek_check gather_step_check ubench sched_variants install clean
+.PHONY: all lib tools oracle dropin asan dbgbar experiments gather_walk_check gather_seek_check gather_step_check pkt_walk_check ubench sched_variants install clean

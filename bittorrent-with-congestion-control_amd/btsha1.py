@@ -124,6 +124,15 @@ class VerifierGatherStats(ctypes.Structure):  # include/bt_sha1.h bt_sha1_verifi
 _sig("bt_sha1_gather_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp)
 _sig("bt_sha1_gather_verify_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
 _sig("bt_sha1_set_segchain_batch", _u64, _u64)
+
+
+class PktGeom(ctypes.Structure):  # include/bt_sha1.h bt_sha1_pkt_geom
+    _fields_ = [(f, ctypes.c_uint32) for f in ("stride", "header", "payload", "slot_pkts")]
+
+
+_sig("bt_sha1_pkts_dev", ctypes.c_int, _vp, ctypes.POINTER(PktGeom), _vp, _vp, _vp, _vp, _u64, _vp, _vp)
+_sig("bt_sha1_pkts_verify_dev", ctypes.c_int, _vp, ctypes.POINTER(PktGeom), _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
+     _vp)
 _sig("bt_sha1_segchain_dev", ctypes.c_int, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, ctypes.c_uint32, _vp)
 _sig("bt_sha1_verifier_create_gather", _vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
      ctypes.c_uint32)
@@ -332,6 +341,22 @@ def gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d
     """gather_dev with the fused compare, as ragged_verify_dev."""
     _check(lib.bt_sha1_gather_verify_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected, d_ok, d_digests,
                                          stream), "bt_sha1_gather_verify_dev")
+
+
+def pkts_dev(d_base, geom, d_slot_off, d_len, d_order, d_order_first, n, d_digests, stream=None):
+    """Message i = d_len[i] (uint32) bytes held in the packet buffers of the
+    slot at d_base + d_slot_off[i] (uint64, a multiple of 4): with geom a
+    PktGeom, byte m lies in buffer d_order[d_order_first[i] + m // payload]
+    (uint32 / uint64) at header + m % payload."""
+    _check(lib.bt_sha1_pkts_dev(d_base, ctypes.byref(geom), d_slot_off, d_len, d_order, d_order_first, n, d_digests,
+                                stream), "bt_sha1_pkts_dev")
+
+
+def pkts_verify_dev(d_base, geom, d_slot_off, d_len, d_order, d_order_first, n, d_expected, d_ok, d_digests=None,
+                    stream=None):
+    """pkts_dev with the fused compare, as ragged_verify_dev."""
+    _check(lib.bt_sha1_pkts_verify_dev(d_base, ctypes.byref(geom), d_slot_off, d_len, d_order, d_order_first, n,
+                                       d_expected, d_ok, d_digests, stream), "bt_sha1_pkts_verify_dev")
 
 
 def segchain_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_expected=None, d_ok=None, d_digests=None,

@@ -476,6 +476,51 @@ int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, con
   return gather_dev(d_base, d_segs, d_seg_first, d_seg_count, n, d_digests, d_expected, d_ok, true, stream);
 }
 
+// Fixed-size packet buffers (k_sha1_pkts).  Everything the launcher would
+// refuse is refused here with a message, before any device call.
+__attribute__((noinline)) static int pkts_dev(const void *d_base, const bt_sha1_pkt_geom *geom, const uint64_t *d_slot_off,
+                    const uint32_t *d_len, const uint32_t *d_order, const uint64_t *d_order_first, uint64_t n,
+                    uint8_t *d_digests, const uint8_t *d_expected, uint8_t *d_ok, bool verify, void *stream) {
+  if (!d_base || !geom || !d_slot_off || !d_len || !d_order || !d_order_first ||
+      (verify ? !d_expected || !d_ok : !d_digests)) {
+    set_err("null pointer");
+    return -1;
+  }
+  if (((geom->stride | geom->header | geom->payload) & 3u) || geom->payload < 64u ||
+      (uint64_t)geom->header + geom->payload > geom->stride || geom->slot_pkts == 0 ||
+      (uint64_t)geom->slot_pkts * geom->stride > (1ull << 32)) {
+    set_err("pkts: geometry %u/%u/%u x %u outside the rule (bt_sha1.h)", geom->stride, geom->header, geom->payload,
+            geom->slot_pkts);
+    return -1;
+  }
+  if (n > BTSHA1_PKTS_MAX) {
+    set_err("pkts: %llu messages exceed the grid limit", (unsigned long long)n);
+    return -1;
+  }
+  if (n == 0) return 0;
+  int dev = 0;
+  BT_CK(hipGetDevice(&dev));
+  DevCtx *c = ctx_for(dev);
+  if (!c) return -1;
+  BT_CK(btsha1_launch_pkts(d_base, &geom->stride, d_slot_off, d_len, d_order, d_order_first, n, d_digests, d_expected,
+                           d_ok, pick_stream(stream)));
+  return 0;
+}
+
+int bt_sha1_pkts_dev(const void *d_base, const bt_sha1_pkt_geom *geom, const uint64_t *d_slot_off,
+                     const uint32_t *d_len, const uint32_t *d_order, const uint64_t *d_order_first, uint64_t n,
+                     uint8_t *d_digests, void *stream) {
+  return pkts_dev(d_base, geom, d_slot_off, d_len, d_order, d_order_first, n, d_digests, nullptr, nullptr, false,
+                  stream);
+}
+
+int bt_sha1_pkts_verify_dev(const void *d_base, const bt_sha1_pkt_geom *geom, const uint64_t *d_slot_off,
+                            const uint32_t *d_len, const uint32_t *d_order, const uint64_t *d_order_first, uint64_t n,
+                            const uint8_t *d_expected, uint8_t *d_ok, uint8_t *d_digests, void *stream) {
+  return pkts_dev(d_base, geom, d_slot_off, d_len, d_order, d_order_first, n, d_digests, d_expected, d_ok, true,
+                  stream);
+}
+
 // Diagnostic, like bt_sha1_column_dev: ONE launch of the chain form of the
 // segment-list kernels whatever bt_sha1_set_segchain_batch says.  What the
 // launcher would refuse is refused here with a message, before any device call.

@@ -52,6 +52,7 @@
 
 #include "sha1_device.h"
 #include "sha1_gather_walk.h"
+#include "sha1_pkt_walk.h"
 #include "sha1_launch.h"
 
 namespace btsha1 {
@@ -1634,6 +1635,60 @@ __global__ __launch_bounds__(128) void k_sha1_gather_lat(const uint8_t *__restri
 }
 
 // ---------------------------------------------------------------------------
+// Fixed-size packet buffers (bt_sha1_pkts_dev): message i lies in the payloads
+// of the packet buffers of slot base + slot_off[i], `g.stride` bytes apart,
+// sequence position k in buffer order[order_first[i] + k].  One message per
+// lane like k_sha1_gather, with no descriptor: the walk from (position, bytes
+// consumed) to blocks is arithmetic, sha1_pkt_walk.h, which also states what
+// is read (nothing outside a clamped buffer's payload area, no order entry at
+// or past the message's count).  One instantiation and one compress: padding
+// blocks go through the loop's own, the fused compare is chosen by
+// ok != nullptr, uniform over the grid.  No LDS, no barrier.  Lanes past n
+// redo the last message and store nothing, so a wave's loop bounds come from
+// real messages only.
+// ---------------------------------------------------------------------------
+struct PktLoads {
+  __device__ __forceinline__ uint32_t order(const uint32_t *p) const { return *p; }
+  __device__ __forceinline__ void quad(PktQuad &q, const uint8_t *p) const { __builtin_memcpy(&q, p, 16); }
+};
+
+__global__ __launch_bounds__(kBlock) void k_sha1_pkts(const uint8_t *__restrict__ base, const PktGeom g,
+                                                      const uint64_t *__restrict__ slot_off,
+                                                      const uint32_t *__restrict__ lens,
+                                                      const uint32_t *__restrict__ order,
+                                                      const uint64_t *__restrict__ order_first, uint64_t n,
+                                                      uint8_t *__restrict__ digests,
+                                                      const uint8_t *__restrict__ expected,
+                                                      uint8_t *__restrict__ ok, uint32_t wg) {
+  // wg = blockDim.x, as an argument: reading blockDim makes the kernel carry
+  // the thirteen hidden arguments in its metadata, 0.6 KB of the library.
+  const uint64_t idx = (uint64_t)blockIdx.x * wg + threadIdx.x;
+  const uint64_t i = idx < n ? idx : n - 1;
+  State st;
+  st.init();
+  PktLoads loads;
+  GatherCompress sink{st};
+  pkt_walk(g, base + slot_off[i], order + order_first[i], lens[i], lens + i, loads, sink);
+  if (idx < n) {
+    // Big-endian words through 4-byte accesses at any alignment (gfx950 under
+    // HSA runs unaligned accesses, SrcBytes above): a quarter of the
+    // instructions of store_digest_bytes, in a library whose size is bounded.
+    const uint32_t h[5] = {bswap(st.h0), bswap(st.h1), bswap(st.h2), bswap(st.h3), bswap(st.h4)};
+    if (digests) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) __builtin_memcpy(digests + idx * 20u + 4 * k, &h[k], 4);
+    }
+    if (ok) {  // memcmp(hash, chunk->hash, 20) == 0, util.c:313
+      uint32_t x[5], diff = 0;
+      __builtin_memcpy(x, expected + idx * 20u, 20);
+#pragma unroll
+      for (int k = 0; k < 5; ++k) diff |= x[k] ^ h[k];
+      ok[idx] = diff == 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Frozen synthetic generator: word g of the stream = splitmix64(seed + g),
 // stored little-endian (mirrored by oracle/sha1_oracle.c:or_fill_synthetic).
 // ---------------------------------------------------------------------------
@@ -2456,6 +2511,20 @@ hipError_t btsha1_launch_gather(const void *base, const void *segs, const uint64
   else
     hipLaunchKernelGGL(k_sha1_gather, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)base,
                        (const GatherSeg *)segs, seg_first, seg_count, n, dig);
+  return hipGetLastError();
+}
+
+// One message per lane, the workgroup width as btsha1_launch_gather's last
+// form.  The arguments were checked by the one caller, bt_runtime.cpp.
+hipError_t btsha1_launch_pkts(const void *base, const uint32_t geom[4], const uint64_t *slot_off, const uint32_t *lens,
+                              const uint32_t *order, const uint64_t *order_first, uint64_t n, uint8_t *dig,
+                              const uint8_t *exp, uint8_t *ok, hipStream_t s) {
+  const PktGeom g{geom[0], geom[1], geom[2], geom[3]};
+  if (n == 0) return hipSuccess;
+  const uint32_t wg = chain_workgroup(n);
+  const uint64_t grid = (n + wg - 1) / wg;
+  hipLaunchKernelGGL(k_sha1_pkts, dim3((uint32_t)grid), dim3(wg), 0, s, (const uint8_t *)base, g, slot_off, lens,
+                     order, order_first, n, dig, exp, ok, wg);
   return hipGetLastError();
 }
 

@@ -144,6 +144,19 @@ BTSHA1_HIDDEN hipError_t btsha1_launch_gather_chain(const void *base, const void
 BTSHA1_HIDDEN void btsha1_set_segchain_batch(uint64_t max_messages);
 BTSHA1_HIDDEN uint64_t btsha1_segchain_batch_setting();
 BTSHA1_HIDDEN uint64_t btsha1_segchain_batch();
+// Fixed-size packet buffers (k_sha1_pkts, one message per lane; the walk and
+// its read contract are sha1_pkt_walk.h): message i is lens[i] bytes held in
+// the slot at base + slot_off[i], sequence position k in packet buffer
+// order[order_first[i] + k]; geom = {stride, header, payload, slot_pkts}
+// (bt_sha1_pkt_geom).  dig / exp / ok as btsha1_launch_gather's, the compare
+// chosen by ok != NULL.  Nothing is checked here: pkts_dev (bt_runtime.cpp),
+// the one caller, refuses null arrays, n above BTSHA1_PKTS_MAX (the grid of
+// the 64-thread form) and geometries outside the rule before it calls.
+#define BTSHA1_PKTS_MAX (0x7fffffffull * 64ull)
+BTSHA1_HIDDEN hipError_t btsha1_launch_pkts(const void *base, const uint32_t geom[4], const uint64_t *slot_off,
+                                            const uint32_t *lens, const uint32_t *order,
+                                            const uint64_t *order_first, uint64_t n, uint8_t *dig, const uint8_t *exp,
+                                            uint8_t *ok, hipStream_t s);
 // The single-message form (grid 1): offset, length and total are kernel
 // arguments, so a host object launches it with no device-side arrays.
 BTSHA1_HIDDEN hipError_t btsha1_launch_resume_one(const void *data, uint32_t len, uint64_t total, uint32_t *state,

@@ -201,6 +201,43 @@ int bt_sha1_gather_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint
 int bt_sha1_gather_verify_dev(const void *d_base, const bt_sha1_seg *d_segs, const uint64_t *d_seg_first,
                               const uint32_t *d_seg_count, uint64_t n, const uint8_t *d_expected,
                               uint8_t *d_ok, uint8_t *d_digests /* may be NULL */, void *stream);
+/* Fixed-size packet buffers (k_sha1_pkts): a chunk hashed where recvmmsg put
+ * its DATA datagrams, an array of equal buffers, with no segment list -- the
+ * host writes one uint32_t per datagram.  A slot is slot_pkts packet buffers
+ * `stride` bytes apart; every datagram of a message carries `payload` bytes
+ * behind a `header`-byte header, its last one what is left.  Message i is
+ * d_len[i] bytes (0: the empty message); with npkt = ceil(len / payload), its
+ * byte m has sequence position k = m / payload, lies in packet buffer
+ * j = d_order[d_order_first[i] + k], at
+ *   d_base + d_slot_off[i] + j*stride + header + m % payload.
+ * Arrival order is free and a duplicate datagram's buffer is simply never
+ * named; positions may name one buffer twice.  d_slot_off[i] must be a
+ * multiple of 4 (the caller's contract: other values give the right digest,
+ * slowly).  Data and arrays may be device or pinned host memory; digests,
+ * d_expected and d_ok take any alignment.
+ * What is read: for message i no byte outside [d_slot_off[i], d_slot_off[i] +
+ * slot_pkts*stride) whatever d_order holds (entries are clamped to
+ * slot_pkts - 1), and no d_order entry at or past npkt; bytes of the slot
+ * outside the listed payloads may be read and influence no result.
+ * -1 with a message, before any device call: a null array (d_expected and
+ * d_ok are both required by the verify form); n above (2^31 - 1) * 64 (the
+ * grid); stride, header or payload not a multiple of 4; payload < 64;
+ * header + payload > stride; slot_pkts == 0; slot_pkts * stride above 2^32.
+ * n == 0 is no work.  Callers with other geometries (odd sizes, short
+ * payloads, headers of varying size) use bt_sha1_gather_dev. */
+typedef struct {
+  uint32_t stride;    /* bytes from one packet buffer to the next             */
+  uint32_t header;    /* bytes in front of the payload in every buffer        */
+  uint32_t payload;   /* payload bytes of every datagram but a message's last */
+  uint32_t slot_pkts; /* packet buffers per slot                              */
+} bt_sha1_pkt_geom;
+int bt_sha1_pkts_dev(const void *d_base, const bt_sha1_pkt_geom *geom /* host */, const uint64_t *d_slot_off,
+                     const uint32_t *d_len, const uint32_t *d_order, const uint64_t *d_order_first, uint64_t n,
+                     uint8_t *d_digests, void *stream);
+int bt_sha1_pkts_verify_dev(const void *d_base, const bt_sha1_pkt_geom *geom /* host */, const uint64_t *d_slot_off,
+                            const uint32_t *d_len, const uint32_t *d_order, const uint64_t *d_order_first,
+                            uint64_t n, const uint8_t *d_expected, uint8_t *d_ok,
+                            uint8_t *d_digests /* may be NULL */, void *stream);
 /* Diagnostic, like bt_sha1_column_dev: ONE launch of the segment-list
  * kernels' chain form (k_sha1_gather_chain: one two-wave workgroup per
  * message, which needs no position table -- it builds one in LDS, a window of

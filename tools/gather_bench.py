@@ -28,7 +28,15 @@ default), with the latency knob on, and with bt_sha1_set_segchain_batch(n)
 (k_sha1_gather_chain, also past the 2 x CUs its auto setting stops at), beside
 bt_sha1_ragged_verify_dev over the same bytes laid out contiguously; the four
 alternate inside each of 7 repetitions, verdicts checked every time.
-usage: gather_bench.py [--host-gib G] [--no-device] [--lat] [--chain] [N ...]
+--pkts: a leg of its own, nothing else runs.  For n = 64, 4096, 32768 (or the
+N given) chunks as 354 datagrams in a shuffled arrival order:
+bt_sha1_pkts_verify_dev (k_sha1_pkts: one uint32 per datagram, no segment
+list) beside bt_sha1_gather_verify_dev with both segment-list knobs off
+(k_sha1_gather_verify, what the same slots launch without it) and
+bt_sha1_ragged_verify_dev over the same bytes contiguous with the latency and
+chain batches at 0 (the lane kernel k_sha1_ragged_verify); the three alternate
+inside each of 7 repetitions, verdicts checked every time.
+usage: gather_bench.py [--host-gib G] [--no-device] [--lat] [--chain] [--pkts] [N ...]
 """
 import argparse
 import json
@@ -167,6 +175,97 @@ def chain_leg(torch, bt, sizes, reps=7):
         del wire, flat, dg, fv, d_seg
 
 
+def pkts_leg(torch, bt, sizes, reps=7):
+    """One JSON line per n; 2 warm-ups, HIP events, the median of `reps`."""
+    for n in sizes or [64, 4096, 32768]:
+        rng = np.random.default_rng(0x9C75 + n)
+        wire = torch.empty(n * SLOT + 16, dtype=torch.uint8, device="cuda")
+        bt.fill_synthetic(wire.data_ptr(), (n * SLOT) & ~15, 0, 0x6A7E)
+        where = np.stack([rng.permutation(NDG) for _ in range(n)]).astype(np.uint64)  # where[i, seq]: arrival place
+        seg = np.zeros((n, NDG, 2), dtype=np.uint64)
+        seg[:, :, 0] = np.arange(n, dtype=np.uint64)[:, None] * SLOT + where * DGRAM + HEADER
+        seg[:, :, 1] = PAYLOAD
+        seg[:, NDG - 1, 1] = LAST
+        idx = torch.from_numpy(where.astype(np.int64)).cuda()
+        flat = torch.empty(n * CHUNK, dtype=torch.uint8, device="cuda")
+        fv = flat.view(n, CHUNK)
+        step = max(1, min(n, 2048))  # the reordered copy, a few chunks at a time
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            dg = wire[lo * SLOT:hi * SLOT].view(hi - lo, NDG, DGRAM)
+            by_seq = torch.gather(dg, 1, idx[lo:hi, :, None].expand(hi - lo, NDG, DGRAM))
+            fv[lo:hi, :(NDG - 1) * PAYLOAD] = by_seq[:, :NDG - 1, HEADER:].reshape(hi - lo, -1)
+            fv[lo:hi, (NDG - 1) * PAYLOAD:] = by_seq[:, NDG - 1, HEADER:HEADER + LAST]
+            del by_seq, dg
+        del idx
+        d_seg = torch.from_numpy(seg.view(np.uint8).reshape(-1)).cuda()
+        d_first = torch.arange(n, dtype=torch.int64, device="cuda") * NDG
+        d_count = torch.full((n,), NDG, dtype=torch.int32, device="cuda")
+        d_order = torch.from_numpy(where.astype(np.uint32).view(np.int32).reshape(-1)).cuda()
+        d_slot = torch.arange(n, dtype=torch.int64, device="cuda") * SLOT
+        d_off = torch.arange(n, dtype=torch.int64, device="cuda") * CHUNK
+        d_len = torch.full((n,), CHUNK, dtype=torch.int32, device="cuda")
+        geom = bt.PktGeom(DGRAM, HEADER, PAYLOAD, NDG)
+        exp = torch.zeros(20 * n, dtype=torch.uint8, device="cuda")
+        bt.ragged_dev(flat.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, exp.data_ptr())
+        torch.cuda.synchronize()
+        exp[20 * (n - 1) + 7] ^= 4  # one chunk fails: a verdict of all ones proves nothing
+        want = torch.ones(n, dtype=torch.uint8, device="cuda")
+        want[n - 1] = 0
+        ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+        def pkts():
+            bt.pkts_verify_dev(wire.data_ptr(), geom, d_slot.data_ptr(), d_len.data_ptr(), d_order.data_ptr(),
+                               d_first.data_ptr(), n, exp.data_ptr(), ok.data_ptr())
+            return "k_sha1_pkts"
+
+        def gather():
+            c, l = bt.set_segchain_batch(0), bt.set_seglist_latency_batch(0)
+            try:
+                bt.gather_verify_dev(wire.data_ptr(), d_seg.data_ptr(), d_first.data_ptr(), d_count.data_ptr(), n,
+                                     exp.data_ptr(), ok.data_ptr())
+                return bt.seglist_kernel_name(n) + "_verify"
+            finally:
+                bt.set_segchain_batch(c)
+                bt.set_seglist_latency_batch(l)
+
+        def lanes():
+            c, l = bt.set_chain_batch(0), bt.set_latency_batch(0)
+            try:
+                bt.ragged_verify_dev(flat.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, exp.data_ptr(),
+                                     ok.data_ptr())
+                return "k_sha1_ragged_verify"
+            finally:
+                bt.set_chain_batch(c)
+                bt.set_latency_batch(l)
+
+        legs = {"pkts": pkts, "gather": gather, "ragged": lanes}
+        names, times = {}, {k: [] for k in legs}
+        for rep in range(2 + reps):
+            for k, fn in legs.items():
+                ok.zero_()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                names[k] = fn()
+                b.record()
+                b.synchronize()
+                assert torch.equal(ok, want), (n, k)
+                if rep >= 2:
+                    times[k].append(a.elapsed_time(b))
+        med = {k: statistics.median(v) for k, v in times.items()}
+        blocks = CHUNK // 64 + 1
+        print(json.dumps({"leg": "pkts", "n": n, "kernels": names,
+                          **{f"{k}_median_ms": round(v, 4) for k, v in med.items()},
+                          **{f"{k}_us_per_block": round(v * 1e3 / blocks, 4) for k, v in med.items()},
+                          "pkts_over_gather": round(med["pkts"] / med["gather"], 3),
+                          "pkts_over_ragged": round(med["pkts"] / med["ragged"], 3),
+                          "gather_over_ragged": round(med["gather"] / med["ragged"], 3),
+                          "pkts_GiB_s": round(n * CHUNK / 2**30 / (med["pkts"] / 1e3), 2),
+                          "ms": {k: [round(x, 4) for x in v] for k, v in times.items()},
+                          "source_id": bt.source_id()}), flush=True)
+        del wire, flat, fv, d_seg, d_order
+
+
 def main():
     import torch
     import btsha1 as bt
@@ -176,11 +275,15 @@ def main():
     ap.add_argument("--no-device", action="store_true")
     ap.add_argument("--lat", action="store_true")
     ap.add_argument("--chain", action="store_true")
+    ap.add_argument("--pkts", action="store_true")
     a = ap.parse_args()
     sizes = a.sizes or [64, 4096, 32768]
     assert (NDG - 1) * PAYLOAD + LAST == CHUNK
     if a.chain:  # a leg of its own: the knobs off and on over the same batches, nothing else
         chain_leg(torch, bt, a.sizes)
+        return
+    if a.pkts:  # likewise
+        pkts_leg(torch, bt, a.sizes)
         return
     if a.host_gib > 0:
         host_paths(torch, bt, a.host_gib)
